@@ -7,7 +7,7 @@ preset for transformer models) -> Johnson TransformerNet forward (bf16 MFMA, fp3
 seeded synthetic checkpoint with the reference's architecture) -> decode + clamp(0,1) +
 ToPILImage truncation -> uint8 frames in HBM.
 
-  python bench.py [--gpus N --steps K --warmup W] [--gather] [--frame 3840x2160]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR] [--gather] [--frame 3840x2160]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
 
 Frames shard round-robin across ranks (each rank its own batch, no data-path collective:
@@ -17,8 +17,10 @@ frames' LAB L planes go to rank 0 in frame order (point-to-point, RCCL over xGMI
 LAB lightness EMA (pipeline.py:1942-1978) over all of them in order and returns each smoothed plane
 to the frame's owner, which rebuilds RGB, blends 0.9 with the original and D2Hs its own frames.
 
-Rank 0 prints ONE JSON line.  The headline K steps run without instrumentation; a separate
-profiled pass (HIP events around every conv launch, on the forward's stream) gives the per-layer
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps (no instrumentation),
+writes the last step's output if --dump-outputs is given, and prints the line.  Everything below runs
+only with --full, after the headline steps: a separate profiled pass (HIP events around every conv
+launch, on the forward's stream) gives the per-layer
 times and the dominant kernel's roofline.  Also reported: the fp32 parity-mode frames/s, and the
 reference CPU path (oracle/nst_oracle.py = the reference's PyTorch-CPU fp32 arithmetic, pinned
 bit-exact to golden vectors of the reference modules) timed on this host per BASELINE.md §4, with
@@ -61,6 +63,14 @@ def parse():
     ap.add_argument("--gather", action="store_true",
                     help="time the video pipeline's exchange with the forward (configs[3]): L planes to rank 0, ordered "
                          "LAB EMA there, planes back to the owners, merge + blend + D2H on the owner")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run everything else this benchmark measures or checks: the "
+                         "full GPU chain and PNG legs, the other precision modes, the profiled per-layer / roofline "
+                         "pass, the graph-vs-eager and --gather self-checks, the fp32 parity mode and the CPU baseline "
+                         "with SSIM (the --no-* options below trim that list)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of the elements where the whole output would pass 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", action=argparse.BooleanOptionalAction, default=True,
                     help="time the step as one HIP-graph replay of the captured forward (engine.capture_u8); "
@@ -273,6 +283,26 @@ def mode_roofline(eng, frames, H: int, W: int, nloc: int) -> dict:
             "per_layer_avg_ms": {n: round(t / max(c, 1), 4) for n, t, c in prof}}
 
 
+DUMP_MAX_BYTES = 48 << 20  # all ranks' --dump-outputs files together (float32), below 64 MB
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir: str, out: torch.Tensor, rank: int, world: int) -> None:
+    """--dump-outputs: what the last timed step returned (this rank's uint8 frames [n, H, W, 3]: the stylized
+    frames in HBM, or with --gather the smoothed and blended frames in page-locked host memory) as float32 in
+    DIR/frames.npy (DIR/frames_rank<r>.npy with more than one rank).  An output over the size budget is
+    sampled: the flattened elements at sorted indices drawn from a fixed seed, which depend only on the output's
+    size, so two builds run with the same arguments write comparable arrays."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = out.reshape(-1)
+    keep = DUMP_MAX_BYTES // 4 // world
+    if flat.numel() > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=keep))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    name = "frames" if world == 1 else f"frames_rank{rank}"
+    np.save(os.path.join(out_dir, name + ".npy"), flat.to(torch.float32).cpu().numpy())
+
+
 def _kernel_sha() -> str:
     from neuralstyletransferv1_amd import _lib
     return _lib.trunk_kernel_sha()
@@ -357,6 +387,7 @@ def main():
                      lambda g: ((1, H * W), torch.uint8), dev, caps)
         for ev in done[-2:]:
             ev.synchronize()
+        return hosts[(len(done) - 1) % 2]  # the last group's final frames on the host
 
     def verify_gather(k=2):
         """--gather self-check, outside the timed region: k more groups through the same schedule with a fresh EMA
@@ -421,7 +452,7 @@ def main():
         t0 = time.perf_counter()
         out = None
         if args.gather:
-            run_gather(k)  # the last group's exchange, EMA, return and D2H belong to the timed work
+            out = run_gather(k)  # the last group's exchange, EMA, return and D2H belong to the timed work
         else:
             for _ in range(k):
                 out = step()
@@ -443,6 +474,61 @@ def main():
     elapsed, out = timed(args.steps)           # the headline: no instrumentation
     total_frames = sum(caps) * args.steps
     fps = total_frames / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
+
+    mp = H * W / 1e6
+    result = {
+        "metric": "stylized 1080p frames/sec at 1/2/4/8 MI355X; SSIM vs CPU ref",
+        "value": round(fps, 3),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16",
+        "data": "synthetic (seeded RGB frames; seeded synthetic Johnson checkpoint with the reference "
+                "architecture: the .pth weights are not shipped)",
+        "config": {
+            "workload": (f"configs[1]: TransformerNet (Johnson) forward, {W}x{H}, batch {BATCH} per GPU, bf16 MFMA / "
+                         f"fp32 accumulate, io_preset {PRESET}, uint8 frames in/out resident in HBM"
+                         + ("; + the video pipeline's exchange (configs[3]): L planes to rank 0, ordered LAB EMA, "
+                            "smoothed planes back to each frame's owner, merge + blend 0.9 + D2H on the owner"
+                            if args.gather else "")),
+            "global_batch": sum(caps),
+            "frame_hw": [H, W],
+            "parallelism": f"frames round-robin over {world} GPU(s), " +
+                           ("point-to-point L-plane gather to rank 0 and return to the owners" if args.gather
+                            else "no data-path collective"),
+            "dist_backend": args.dist_backend if pg else None,
+            "ranks_per_gpu": (world if args.device is not None else 1) if world > 1 else 1,
+            "step_launch": ("one HIP-graph replay of the captured forward per step" if (args.graph and not args.gather)
+                            else "eager kernel launches"),
+        },
+        "whole_path": {
+            "gflop_per_frame": FLOP_PER_PIXEL * H * W / 1e9,
+            "achieved_tflops": round(fps / world * FLOP_PER_PIXEL * H * W / 1e12, 2),
+            "frac_of_mfma_peak": round(fps / world * FLOP_PER_PIXEL * H * W / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
+            "algorithmic_hbm_gbs": round(fps / world * BYTES_PER_PIXEL * H * W / 1e9, 1),
+            "frac_of_hbm_peak": round(fps / world * BYTES_PER_PIXEL * H * W / 1e9 / HBM_PEAK_GBS, 4),
+            "megapixels_per_frame": mp,
+        },
+        "cpu_baseline": None,
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if pg:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:  # a plain run ends here: set-up, warm-up, the timed steps, the result line
+        finish()
+        return
 
     def time_steps(fn, k):
         fn()
@@ -547,37 +633,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             traffic_note = f"unreadable PMC summary: {e}"
 
-    mp = H * W / 1e6
-    result = {
-        "metric": "stylized 1080p frames/sec at 1/2/4/8 MI355X; SSIM vs CPU ref",
-        "value": round(fps, 3),
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16",
-        "data": "synthetic (seeded RGB frames; seeded synthetic Johnson checkpoint with the reference "
-                "architecture: the .pth weights are not shipped)",
-        "config": {
-            "workload": (f"configs[1]: TransformerNet (Johnson) forward, {W}x{H}, batch {BATCH} per GPU, bf16 MFMA / "
-                         f"fp32 accumulate, io_preset {PRESET}, uint8 frames in/out resident in HBM"
-                         + ("; + the video pipeline's exchange (configs[3]): L planes to rank 0, ordered LAB EMA, "
-                            "smoothed planes back to each frame's owner, merge + blend 0.9 + D2H on the owner"
-                            if args.gather else "")),
-            "global_batch": sum(caps),
-            "frame_hw": [H, W],
-            "parallelism": f"frames round-robin over {world} GPU(s), " +
-                           ("point-to-point L-plane gather to rank 0 and return to the owners" if args.gather
-                            else "no data-path collective"),
-            "dist_backend": args.dist_backend if pg else None,
-            "ranks_per_gpu": (world if args.device is not None else 1) if world > 1 else 1,
-            "step_launch": ("one HIP-graph replay of the captured forward per step" if (args.graph and not args.gather)
-                            else "eager kernel launches"),
-        },
+    result.update({
         "roofline": {
             "bound": "mfma",
             "kernel": (f"wst16_kernel<bf16, 8, WF_NORM> (conv_wst16.hip: residual-trunk conv 3x3 128->128 on 16x16x32 MFMAs, "
@@ -615,20 +671,13 @@ def main():
                 "algorithmic_bytes_per_launch": 2 * res_bytes,
             },
         },
-        "whole_path": {
-            "gflop_per_frame": FLOP_PER_PIXEL * H * W / 1e9,
-            "achieved_tflops": round(fps / world * FLOP_PER_PIXEL * H * W / 1e12, 2),
-            "frac_of_mfma_peak": round(fps / world * FLOP_PER_PIXEL * H * W / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
-            "algorithmic_hbm_gbs": round(fps / world * BYTES_PER_PIXEL * H * W / 1e9, 1),
-            "frac_of_hbm_peak": round(fps / world * BYTES_PER_PIXEL * H * W / 1e9 / HBM_PEAK_GBS, 4),
+        "whole_path": {**result["whole_path"],
             "profiled_steps": kp,
             "conv_kernel_ms_per_step": round(conv_ms_per_step, 3),
             "trunk_joined_avg_ms": round(joined_avg_ms, 4),
             "per_layer_avg_ms": layer_ms,
-            "megapixels_per_frame": mp,
         },
-        "cpu_baseline": None,
-    }
+    })
     if chain_s is not None:
         result["gpu_full_chain"] = {
             "frames_per_s": round(nloc / chain_s, 2),
@@ -683,11 +732,7 @@ def main():
                 "within_1lsb_values": round(float(np.mean([(d <= 1).mean() for d in da])), 6),
                 "within_1lsb_pixels": round(float(np.mean([(d.max(-1) <= 1).mean() for d in da])), 6),
             })
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if pg:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

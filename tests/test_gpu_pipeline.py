@@ -334,7 +334,7 @@ def test_bench_two_ranks_under_torchrun_gloo(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
            "--warmup", "1", "--gather", "--dist-backend", "gloo", "--device", "0", "--frame", "960x540",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path),
                        env=dict(os.environ, OMP_NUM_THREADS="4"))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -358,12 +358,48 @@ def test_bench_gather_self_check_one_rank(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--gather",
-                        "--frame", "960x540", "--no-cpu-baseline", "--no-fp32", "--no-fp16", "--no-fp16m", "--no-fp32s"],
+                        "--frame", "960x540", "--no-cpu-baseline", "--no-fp32", "--no-fp16", "--no-fp16m", "--no-fp32s", "--full"],
                        capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     v = d["gather_verify"]
     assert v["ranks"] == 1 and v["planes_match"] and v["frames_match"], v
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain bench.py run (--gpus 1 --steps N --warmup W) times N steps and prints the headline line without the
+    --full legs; --dump-outputs writes the last timed step's frames as float32, and they are what the engine
+    returns for the bench's seeded frames and checkpoint (the graph replay is bit-exact against the eager forward)."""
+    import json
+    import subprocess
+    import sys
+    from neuralstyletransferv1_amd.transformer_net import TransformerNet
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d_out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--frame", "192x108", "--dump-outputs", str(d_out)],
+                       capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    for key in ("roofline", "gpu_full_chain", "gpu_png_encode", "fp16_mode", "fp32_parity_frames_per_s",
+                "graph_step_matches_eager", "ssim_vs_cpu"):
+        assert key not in d, key
+    assert d["cpu_baseline"] is None
+    assert [p.name for p in d_out.iterdir()] == ["frames.npy"]
+    got = np.load(d_out / "frames.npy")
+    assert got.dtype == np.float32 and got.shape == (8 * 108 * 192 * 3,)
+    dev = torch.device("cuda", 0)
+    net = TransformerNet()
+    net.load_state_dict(synthetic.make_state_dict("johnson", seed=0))
+    net = net.to(dev).eval()
+    net.compute_dtype = "bf16"
+    frames = torch.from_numpy(synthetic.make_frames(8, 108, 192, seed=1000)).to(dev)
+    want = net.engine(dev).stylize_u8(frames, "imagenet_255").cpu().numpy()
+    assert np.array_equal(got, want.reshape(-1).astype(np.float32))
 
 
 def test_input_dir_staging_in_memory_jpeg_exif_png(tmp_path):

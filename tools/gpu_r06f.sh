@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${1:-r06_f}
 bash tools/gpu_all.sh $TAG || exit 1
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --gather --no-cpu-baseline --no-fp32 --no-fp16 --no-fp16m --no-fp32s \
+timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --gather --full --no-cpu-baseline --no-fp32 --no-fp16 --no-fp16m --no-fp32s \
   > gpurun_out/bench_gather_$TAG.json 2> gpurun_out/bench_gather_$TAG.err || { echo "gather bench failed"; tail -20 gpurun_out/bench_gather_$TAG.err; exit 1; }
 python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().splitlines()[-1]); print('gather', d['value'], d['gather_verify'])" gpurun_out/bench_gather_$TAG.json
 for i in 1 2 3; do

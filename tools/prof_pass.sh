@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R" || exit 1
 export TMPDIR=/tmp
 TAG=$1; shift
-ARGS=${*:---steps 3 --warmup 1 --no-cpu-baseline --no-fp32}
+ARGS=${*:---steps 3 --warmup 1 --full --no-cpu-baseline --no-fp32}
 O=gpurun_out/$TAG
 mkdir -p "$O"
 run() {  # name, then rocprofv3 options
