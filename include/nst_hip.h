@@ -542,6 +542,34 @@ int nst_png_workspace_bytes(int n, int h, int w, int c, size_t* out);
 int nst_png_encode_u8(const uint8_t* frames, int n, int h, int w, int c, uint8_t* out, size_t out_stride,
                       int64_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- JPEG decode of the extracted frames (pipeline.py:401-408 writes them with ffmpeg -c:v mjpeg, :1086 opens each
+ * with Pillow; --jpeg_reader gpu) ----
+ * Split in two.  The host half (no HIP call, no global state, thread-safe) entropy-decodes one baseline stream into
+ * a coefficient record; the device half turns n records of one geometry into u8 frames [n,h,w,3] that equal
+ * Pillow's Image.open(f).convert("RGB") byte for byte (libjpeg-turbo defaults: islow IDCT, fancy upsampling).
+ *
+ * Fast path: SOF0 (baseline, 8-bit, Huffman), 8-bit quantisation tables, one scan holding every component; 1
+ * component, or 3 with ids 1,2,3 (JFIF YCbCr), chroma 1x1 and luma 1x1 / 2x1 / 2x2; DRI / RSTn; APPn and COM
+ * skipped, except that an Adobe APP14 marker is refused.  Every other stream -> NST_E_SHAPE; a stream that does not
+ * decode completely and cleanly (bad code, coefficient index past 63, premature marker, truncation, no EOI after
+ * the last MCU) -> NST_E_DATA.  Either way the caller hands the file to its usual decoder.
+ *
+ * Record of one frame (record_bytes from nst_jpeg_probe; a multiple of 16): uint16 qt[3][64], the dequantisation
+ * table of each component in natural order, then int16 coef[blocks][64] in natural order, planar by component, each
+ * plane's blocks (the MCU grid's padding included) in raster order.  sampling: NST_JPEG_444 also for 1 component. */
+#define NST_E_DATA (-7) /* damaged input stream */
+#define NST_JPEG_444 0
+#define NST_JPEG_422 1 /* luma 2x1 (h2v1) */
+#define NST_JPEG_420 2 /* luma 2x2 (h2v2) */
+int nst_jpeg_probe(const uint8_t* data, size_t len, int* h, int* w, int* comps, int* sampling, size_t* record_bytes);
+/* record: caller memory (2-byte aligned, e.g. page-locked) of exactly the probed record_bytes */
+int nst_jpeg_entropy_decode(const uint8_t* data, size_t len, void* record, size_t record_bytes);
+int nst_jpeg_workspace_bytes(int n, int h, int w, int comps, int sampling, size_t* out);
+/* records: n records back to back on the device (16-byte aligned), all of (h, w, comps, sampling); out u8 [n,h,w,3]
+ * (4-byte aligned; a single component gives R = G = B); n*h*w < 2^31.  Two launches on `stream`, nothing else. */
+int nst_jpeg_reconstruct_u8(const void* records, size_t record_bytes, int n, int h, int w, int comps, int sampling,
+                            uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

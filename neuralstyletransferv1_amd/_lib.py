@@ -50,7 +50,10 @@ EXPORTED_SYMBOLS = (
     "nst_flow_dis_scratch_bytes", "nst_flow_dis", "nst_set_range_check", "nst_input_exact", "nst_set_stream_split",
     "nst_lab_planes_u8", "nst_lab_ema_planes", "nst_lab_merge_u8",
     "nst_png_bound", "nst_png_workspace_bytes", "nst_png_encode_u8",
+    "nst_jpeg_probe", "nst_jpeg_entropy_decode", "nst_jpeg_workspace_bytes", "nst_jpeg_reconstruct_u8",
 )
+NST_E_INVALID, NST_E_SHAPE, NST_E_WORKSPACE, NST_E_DATA = -1, -3, -5, -7
+NST_JPEG_444, NST_JPEG_422, NST_JPEG_420 = 0, 1, 2
 # region compositor limits / geometry kinds (include/nst_hip.h NST_REGION_*, NST_RG_*)
 NST_REGION_MAX, NST_REGION_TERMS, NST_REGION_MAX_SRC = 32, 9, 16
 RG_KINDS = {"rects": 0, "diagonal": 1, "voronoi": 2, "radial": 3, "waves": 4, "spiral": 5, "concentric": 6}
@@ -223,6 +226,14 @@ def lib() -> ctypes.CDLL:
         L.nst_png_bound.argtypes = [i, i, i, ctypes.POINTER(sz)]
         L.nst_png_workspace_bytes.argtypes = [i, i, i, i, ctypes.POINTER(sz)]
         L.nst_png_encode_u8.argtypes = [vp, i, i, i, i, vp, sz, vp, vp, sz, vp]
+        psz = ctypes.POINTER(sz)
+        L.nst_jpeg_probe.argtypes = [vp, sz, pi, pi, pi, pi, psz]
+        L.nst_jpeg_entropy_decode.argtypes = [vp, sz, vp, sz]
+        L.nst_jpeg_workspace_bytes.argtypes = [i, i, i, i, i, psz]
+        L.nst_jpeg_reconstruct_u8.argtypes = [vp, sz, i, i, i, i, i, vp, vp, sz, vp]
+        for name in ("nst_jpeg_probe", "nst_jpeg_entropy_decode", "nst_jpeg_workspace_bytes",
+                     "nst_jpeg_reconstruct_u8"):
+            getattr(L, name).restype = i
         for name in ("nst_png_bound", "nst_png_workspace_bytes", "nst_png_encode_u8"):
             getattr(L, name).restype = i
         for name in ("nst_lab_planes_u8", "nst_lab_ema_planes", "nst_lab_merge_u8", "nst_input_exact"):

@@ -177,6 +177,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "built on the GPU that styled the frame (csrc/png_enc.hip: Up filter, per-scanline dynamic "
                          "Huffman blocks, CRC and Adler-32 on the device), the host only writes bytes.  The pixels are "
                          "identical either way")
+    ap.add_argument("--jpeg_reader", choices=["pil", "gpu"], default="pil",
+                    help="JPEG frames of the frame loop: 'pil' (default) = Pillow's decoder, as the reference; 'gpu' = "
+                         "baseline JPEG files (what ffmpeg's mjpeg and Pillow write) are only entropy-decoded on the "
+                         "host pool (csrc/jpeg_entropy.cpp) and rebuilt on the GPU (csrc/jpeg_dec.hip: IDCT, chroma "
+                         "upsampling, colour conversion).  The pixels are Pillow's, byte for byte; any other file, a "
+                         "damaged one, --inference_res and --input_dir staging keep Pillow")
     ap.add_argument("--png_compress_level", type=int, default=None, choices=range(10), metavar="0-9",
                     help="Pillow's PNG encoder at this zlib level (overrides --png_writer); the pixels are the same "
                          "at every level, only the file size and the encode time change")
@@ -590,6 +596,28 @@ def style_frames(args, frames_dir: Optional[Path], model_path, output_prefix: st
     prefetch_depth = 2
 
     pinned = {}  # shard k -> page-locked [n, h, w, 3] the loaders decode into (one H2D copy per group, async)
+    # --jpeg_reader gpu: shard k -> (page-locked coefficient records [n, record_bytes], JpegInfo); the loaders only
+    # entropy-decode, the GPU rebuilds the frames (jpegio.py).  Not with --inference_res (host LANCZOS needs the
+    # pixels) or --input_dir staging (EXIF / re-encode round trip): those keep Pillow
+    jpeg_recs = {}
+    jpeg_gpu = (getattr(args, "jpeg_reader", "pil") == "gpu" and src.files is not None and src.staged is None
+                and src.infer_res == 0)
+
+    def _jpeg_shard(sh):
+        """the shard's file bytes and common JpegInfo when every frame is a fast-path JPEG of one geometry"""
+        from . import jpegio
+        if any(Path(src.files[f]).suffix.lower() not in (".jpg", ".jpeg") for f in sh):
+            return None
+        datas, info = [], None
+        for f in sh:
+            with open(src.files[f], "rb") as fh:
+                d = fh.read()
+            i = jpegio.probe(d)
+            if i is None or (info is not None and i != info) or (i.h, i.w) != tuple(sizes[f]):
+                return None
+            info = i
+            datas.append(d)
+        return datas, info
 
     def _load_into(f, buf, j):
         a, b = src.load(f)
@@ -600,7 +628,16 @@ def style_frames(args, frames_dir: Optional[Path], model_path, output_prefix: st
         if 0 <= k < len(my_shards) and my_shards[k] and k not in pinned:
             sh = my_shards[k]
             h0, w0 = sizes[sh[0]]
-            if all(sizes[f] == (h0, w0) for f in sh):
+            js = _jpeg_shard(sh) if jpeg_gpu else None
+            if js is not None:
+                from . import jpegio
+                rec = torch.empty((len(sh), js[1].record_bytes), dtype=torch.uint8, pin_memory=True)
+                pinned[k] = None
+                jpeg_recs[k] = (rec, js[1])
+                rn = rec.numpy()
+                for j, f in enumerate(sh):  # -> 0, or a code: the stream is not clean and the shard goes to Pillow
+                    loads[f] = pool.submit(jpegio.entropy_decode_into, js[0][j], rn[j])
+            elif all(sizes[f] == (h0, w0) for f in sh):
                 buf = torch.empty((len(sh), h0, w0, 3), dtype=torch.uint8, pin_memory=True)
                 pinned[k] = buf
                 bn = buf.numpy()
@@ -624,10 +661,17 @@ def style_frames(args, frames_dir: Optional[Path], model_path, output_prefix: st
         for j in range(k, k + 1 + prefetch_depth):
             _submit(j)
         buf = pinned.pop(k, None)
+        jrec = jpeg_recs.pop(k, None)
         with prof("wait_decode"):
             loaded = [(loads.pop(f) if f in loads else pool.submit(src.load, f)).result() for f in idx]
+            if jrec is not None and any(loaded):  # Pillow warns, raises or decodes the damaged file as it always did
+                jrec = None
+                loaded = [t.result() for t in [pool.submit(src.load, f) for f in idx]]
         with prof("h2d"):
-            if buf is not None:  # decoded straight into page-locked memory; loaded = the model inputs if different
+            if jrec is not None:
+                from . import jpegio
+                orig = xin = jpegio.reconstruct_gpu(jrec[0].to(dev, non_blocking=True), jrec[1])
+            elif buf is not None:  # decoded straight into page-locked memory; loaded = the model inputs if different
                 orig = buf.to(dev, non_blocking=True)
                 xin = orig if loaded[0] is None else torch.from_numpy(np.stack(loaded)).to(dev)
             else:
