@@ -570,6 +570,25 @@ int nst_jpeg_workspace_bytes(int n, int h, int w, int comps, int sampling, size_
 int nst_jpeg_reconstruct_u8(const void* records, size_t record_bytes, int n, int h, int w, int comps, int sampling,
                             uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- JPEG encode of the styled frames (pipeline.py:2099-2113 `out_img.save(out_path, format="JPEG",
+ * quality=int(jpeg_quality))`; --jpeg_writer gpu) ----
+ * n u8 RGB frames [n,h,w,3] (device) -> n complete JPEG files, file j at out + j*out_stride, its byte count in
+ * sizes[j] (int64, device).  Each file equals what Pillow (libjpeg-turbo defaults) writes for that frame and quality
+ * byte for byte: JFIF 1.1 APP0 (units 0, density 1:1), two DQT, baseline SOF0 at 4:2:0, the four standard DHT, one
+ * interleaved scan without restart markers, EOI.  The whole file is built on the device (colour, h2v2 downsample,
+ * islow FDCT, quantise, Huffman coding, 0xFF stuffing); the host only writes bytes.
+ *
+ * quality 1..100; h, w 1..65535 and at most 2^21 8x8 blocks per frame (a frame's bit count stays below 2^32); out,
+ * out_stride and workspace 16-byte aligned.  out_stride may be below nst_jpeg_enc_bound (the worst case of any
+ * content): a frame whose file does not fit its slot gets sizes[j] = -1, nothing is written outside its slot, and the
+ * other frames' files are complete.  Bytes of a slot past sizes[j] are undefined.  Workspace per
+ * nst_jpeg_enc_workspace_bytes (a smaller one is NST_E_INVALID, like every other bad argument, before any GPU call).
+ * Every launch goes on `stream`; no allocation, no copy, no host synchronisation. */
+int nst_jpeg_enc_bound(int h, int w, size_t* out_stride);
+int nst_jpeg_enc_workspace_bytes(int n, int h, int w, size_t* out);
+int nst_jpeg_encode_u8(const uint8_t* frames, int n, int h, int w, int quality, uint8_t* out, size_t out_stride,
+                       int64_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

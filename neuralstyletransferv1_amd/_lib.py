@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "nst_lab_planes_u8", "nst_lab_ema_planes", "nst_lab_merge_u8",
     "nst_png_bound", "nst_png_workspace_bytes", "nst_png_encode_u8",
     "nst_jpeg_probe", "nst_jpeg_entropy_decode", "nst_jpeg_workspace_bytes", "nst_jpeg_reconstruct_u8",
+    "nst_jpeg_enc_bound", "nst_jpeg_enc_workspace_bytes", "nst_jpeg_encode_u8",
 )
 NST_E_INVALID, NST_E_SHAPE, NST_E_WORKSPACE, NST_E_DATA = -1, -3, -5, -7
 NST_JPEG_444, NST_JPEG_422, NST_JPEG_420 = 0, 1, 2
@@ -231,8 +232,12 @@ def lib() -> ctypes.CDLL:
         L.nst_jpeg_entropy_decode.argtypes = [vp, sz, vp, sz]
         L.nst_jpeg_workspace_bytes.argtypes = [i, i, i, i, i, psz]
         L.nst_jpeg_reconstruct_u8.argtypes = [vp, sz, i, i, i, i, i, vp, vp, sz, vp]
+        L.nst_jpeg_enc_bound.argtypes = [i, i, psz]
+        L.nst_jpeg_enc_workspace_bytes.argtypes = [i, i, i, psz]
+        L.nst_jpeg_encode_u8.argtypes = [vp, i, i, i, i, vp, sz, vp, vp, sz, vp]
         for name in ("nst_jpeg_probe", "nst_jpeg_entropy_decode", "nst_jpeg_workspace_bytes",
-                     "nst_jpeg_reconstruct_u8"):
+                     "nst_jpeg_reconstruct_u8", "nst_jpeg_enc_bound", "nst_jpeg_enc_workspace_bytes",
+                     "nst_jpeg_encode_u8"):
             getattr(L, name).restype = i
         for name in ("nst_png_bound", "nst_png_workspace_bytes", "nst_png_encode_u8"):
             getattr(L, name).restype = i

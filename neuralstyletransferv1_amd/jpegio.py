@@ -10,6 +10,10 @@ upsampling, YCbCr -> RGB, NHWC store (csrc/jpeg_dec.hip, nst_jpeg_reconstruct_u8
 The fast path takes what ffmpeg and Pillow write by default (include/nst_hip.h "JPEG decode" lists it); `probe`
 returns None for every other stream and `entropy_decode_into` returns a non-zero code for a damaged one, and the
 caller decodes those with Pillow as before.
+
+The writer (`--jpeg_writer gpu`) has no host half: `encode_jpeg_gpu` builds the reference's output files
+(pipeline.py:2099-2113, `out_img.save(out_path, format="JPEG", quality=...)`) whole on the GPU, byte for byte what
+Pillow writes (csrc/jpeg_enc.hip, nst_jpeg_encode_u8; tests/test_jpeg_enc_host.py, tests/test_gpu_jpeg_enc.py).
 """
 from __future__ import annotations
 
@@ -100,3 +104,64 @@ def decode_gpu(files, device):
     for j, d in enumerate(files):
         _lib.check(entropy_decode_into(d, hn[j]), "nst_jpeg_entropy_decode")
     return reconstruct_gpu(host.to(device, non_blocking=True), info)
+
+
+# ---- JPEG writer on the GPU (`--jpeg_writer gpu`) ----
+_enc_ws = {}  # (device, n, h, w) -> workspace tensor, reused across groups
+
+
+def jpeg_enc_bound(h: int, w: int) -> int:
+    """Worst-case size of one h x w file from the GPU writer (nst_jpeg_enc_bound; a multiple of 16)."""
+    from . import _lib
+    bound = ctypes.c_size_t()
+    _lib.check(_lib.lib().nst_jpeg_enc_bound(h, w, ctypes.byref(bound)), "nst_jpeg_enc_bound")
+    return bound.value
+
+
+def jpeg_enc_workspace_bytes(n: int, h: int, w: int) -> int:
+    from . import _lib
+    wsb = ctypes.c_size_t()
+    _lib.check(_lib.lib().nst_jpeg_enc_workspace_bytes(n, h, w, ctypes.byref(wsb)), "nst_jpeg_enc_workspace_bytes")
+    return wsb.value
+
+
+def encode_jpeg_gpu(frames_u8, quality: int, out_stride: Optional[int] = None):
+    """uint8 RGB frames [n,h,w,3] on an MI355X -> (files [n, stride] uint8, sizes [n] int64), both on the device,
+    on the current stream: file j is files[j, :sizes[j]] and equals what Pillow's
+    Image.fromarray(frame).save(f, format="JPEG", quality=quality) writes (csrc/jpeg_enc.hip, nst_jpeg_encode_u8).
+    `out_stride` (a multiple of 16; default the worst case of any content) may be smaller than that bound: a frame
+    whose file does not fit gets sizes[j] == -1 and the caller encodes it another way.  No CPU path."""
+    import torch
+
+    from . import _lib
+    _lib.require_gpu_tensor(frames_u8, "encode_jpeg_gpu frames")
+    x = frames_u8
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f"encode_jpeg_gpu: need uint8 [n,h,w,3], got {x.dtype} {tuple(x.shape)}")
+    x = x.contiguous()
+    n, h, w, _ = x.shape
+    L = _lib.lib()
+    stride = jpeg_enc_bound(h, w) if out_stride is None else int(out_stride)
+    wsb = jpeg_enc_workspace_bytes(n, h, w)
+    key = (x.device, n, h, w)
+    ws = _enc_ws.get(key)
+    if ws is None:
+        if len(_enc_ws) > 4:
+            _enc_ws.clear()
+        ws = _enc_ws[key] = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+    files = torch.empty((n, stride), dtype=torch.uint8, device=x.device)
+    sizes = torch.empty(n, dtype=torch.int64, device=x.device)
+    _lib.check(L.nst_jpeg_encode_u8(x.data_ptr(), n, h, w, int(quality), files.data_ptr(), stride, sizes.data_ptr(),
+                                    ws.data_ptr(), wsb, _lib.stream_ptr(x.device)), "nst_jpeg_encode_u8")
+    cur = torch.cuda.current_stream(x.device)
+    ws.record_stream(cur)
+    x.record_stream(cur)
+    return files, sizes
+
+
+def jpeg_bytes_gpu(frames_u8, quality: int) -> list:
+    """encode_jpeg_gpu, copied to the host: one bytes object (a complete JPEG file) per frame."""
+    files, sizes = encode_jpeg_gpu(frames_u8, quality)
+    sz = sizes.cpu().tolist()
+    host = files.cpu().numpy()
+    return [host[j, :sz[j]].tobytes() for j in range(len(sz))]

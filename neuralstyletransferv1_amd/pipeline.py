@@ -183,6 +183,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "host pool (csrc/jpeg_entropy.cpp) and rebuilt on the GPU (csrc/jpeg_dec.hip: IDCT, chroma "
                          "upsampling, colour conversion).  The pixels are Pillow's, byte for byte; any other file, a "
                          "damaged one, --inference_res and --input_dir staging keep Pillow")
+    ap.add_argument("--jpeg_writer", choices=["pil", "gpu"], default="pil",
+                    help="JPEG outputs: 'pil' (default) = Pillow's encoder at --jpeg_quality, as the reference; 'gpu' = "
+                         "the whole file built on the GPU that styled the frame (csrc/jpeg_enc.hip: colour conversion, "
+                         "4:2:0 downsampling, FDCT, quantisation, Huffman coding and 0xFF stuffing on the device), the "
+                         "host only writes bytes.  The files are Pillow's, byte for byte; a --jpeg_quality outside "
+                         "1..100 and a frame whose file outgrows the copied slot keep Pillow")
     ap.add_argument("--png_compress_level", type=int, default=None, choices=range(10), metavar="0-9",
                     help="Pillow's PNG encoder at this zlib level (overrides --png_writer); the pixels are the same "
                          "at every level, only the file size and the encode time change")
@@ -795,30 +801,40 @@ def style_frames(args, frames_dir: Optional[Path], model_path, output_prefix: st
                                       args.composite_mode)
         gpu_png = (getattr(args, "png_writer", "pil") == "gpu" and not args.no_save
                    and getattr(args, "png_compress_level", None) is None and not any(_out_path(f)[1] for f in idx))
+        # --jpeg_writer gpu: per group, when every frame of it is saved as a JPEG at a quality libjpeg takes as given
+        gpu_jpeg = (getattr(args, "jpeg_writer", "pil") == "gpu" and not args.no_save
+                    and 1 <= int(jpeg_quality) <= 100 and all(_out_path(f)[1] for f in idx))
+        gpu_files = gpu_png or gpu_jpeg
         with prof("d2h"):
             # page-locked D2H on a copy stream behind the frames' last kernel; the encoders wait for its event, so
-            # this thread goes on queueing the next group's forward instead of waiting for the GPU.  --png_writer gpu:
-            # the group's finished PNG files (and their sizes) instead of the pixels
+            # this thread goes on queueing the next group's forward instead of waiting for the GPU.  --png_writer gpu
+            # and --jpeg_writer gpu: the group's finished files (and their sizes) instead of the pixels
             if gpu_png:
                 from .pngio import encode_png_gpu
                 src, sizes_d = encode_png_gpu(styled)
+            elif gpu_jpeg:
+                from .jpegio import encode_jpeg_gpu
+                src, sizes_d = encode_jpeg_gpu(styled, int(jpeg_quality),
+                                               _jpeg_slot_bytes(styled.shape[1], styled.shape[2]))
             else:
                 src, sizes_d = styled, None
             host_t = torch.empty(src.shape, dtype=torch.uint8, pin_memory=True)
-            host_sz = torch.empty(src.shape[0], dtype=torch.int64, pin_memory=True) if gpu_png else None
+            host_sz = torch.empty(src.shape[0], dtype=torch.int64, pin_memory=True) if gpu_files else None
             copy_stream.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(copy_stream):
                 host_t.copy_(src, non_blocking=True)
-                if gpu_png:
+                if gpu_files:
                     host_sz.copy_(sizes_d, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(copy_stream)
             src.record_stream(copy_stream)
-            if gpu_png:
+            if gpu_files:
                 sizes_d.record_stream(copy_stream)
         # one waiter thread per run waits for the copy's event and then hands the frames to the encoder pool, so no
-        # pool thread sits blocked on the GPU (the pool also decodes the next groups)
-        pending.append(waiter.submit(_hand_off, ev, host_t, list(idx) if not args.no_save else [], host_sz))
+        # pool thread sits blocked on the GPU (the pool also decodes the next groups).  A JPEG group keeps its pixels
+        # on the device until then: a frame whose file outgrew the copied slot is saved from them
+        pending.append(waiter.submit(_hand_off, ev, host_t, list(idx) if not args.no_save else [], host_sz,
+                                     styled if gpu_jpeg else None))
         del host_t  # the waiter holds it until the copy is done; the savers' row views keep it alive after that
         _reap_pending()
         if not args.no_save:
@@ -876,14 +892,22 @@ def style_frames(args, frames_dir: Optional[Path], model_path, output_prefix: st
     copy_stream = torch.cuda.Stream(dev)
     waiter = ThreadPoolExecutor(max_workers=1)
 
-    def _hand_off(ev, host_t, idx, host_sz=None):
+    def _hand_off(ev, host_t, idx, host_sz=None, styled=None):
         ev.synchronize()
         host = host_t.numpy()
         # each save holds a row view of the page-locked buffer (numpy keeps the tensor as the view's base), so the
         # buffer is released when the group's last save ends -- not held for the whole run
-        if host_sz is not None:  # finished PNG files from the GPU: write their bytes
+        if host_sz is not None:  # finished PNG / JPEG files from the GPU: write their bytes
             sz = host_sz.tolist()
-            return [pool.submit(_write_file, host[j, :sz[j]], f) for j, f in enumerate(idx)]
+            futs = []
+            for j, f in enumerate(idx):
+                if sz[j] >= 0:
+                    futs.append(pool.submit(_write_file, host[j, :sz[j]], f))
+                else:  # the JPEG did not fit its slot (-1): the frame's pixels, encoded on the host as without the flag
+                    with torch.cuda.stream(copy_stream):
+                        px = styled[j].cpu().numpy()
+                    futs.append(pool.submit(_save, px, f))
+            return futs
         return [pool.submit(_save, host[j], f) for j, f in enumerate(idx)]
 
     saves = []  # save futures of handed-off groups, reaped as they finish (errors surface at the next reap)
@@ -970,6 +994,14 @@ def style_frames(args, frames_dir: Optional[Path], model_path, output_prefix: st
                        "setup_seconds": t_start - t_setup}, fh)
     if rank == 0:
         _log(f"Styled {len(src)}/{len(src)} frames in {el:.2f}s ({len(src) / max(el, 1e-9):.2f} frames/s)")
+
+
+def _jpeg_slot_bytes(h: int, w: int) -> int:
+    """--jpeg_writer gpu: bytes copied to the host per frame -- the encoder's worst case, but never more than the
+    frame's pixels (rounded up to the 16 bytes the encoder wants), so the copy is no larger than without the flag.
+    A file that outgrows the slot (nst_jpeg_encode_u8 reports -1) is encoded on the host instead."""
+    from .jpegio import jpeg_enc_bound
+    return min(jpeg_enc_bound(h, w), (h * w * 3 + 15) // 16 * 16)
 
 
 class _PipeProf:

@@ -14,6 +14,7 @@ Default CLI settings (bf16, --batch 8, --blend 0.9, --smooth_alpha 0.65, staged/
 noise, neuralstyletransferv1_amd/synthetic.py).  The timed run excludes the model load (a warm-up run first).
 
   python tools/cli_bench.py [--frames 240] [--threads 16] [--png_writer fast|pil|gpu] [--jpeg_reader pil|gpu]
+      [--jpeg_writer pil|gpu]
 """
 from __future__ import annotations
 
@@ -82,6 +83,7 @@ def main():
                     help="the CLI's PNG writer; the host-only encode rate beside it uses pngio's writer for fast/gpu")
     ap.add_argument("--jpeg_reader", default="pil", choices=["pil", "gpu"],
                     help="the CLI's JPEG frame reader (frames_dir path; --input_dir staging always decodes with Pillow)")
+    ap.add_argument("--jpeg_writer", default="pil", choices=["pil", "gpu"], help="the CLI's JPEG writer")
     ap.add_argument("--formats", default="jpg,png")
     ap.add_argument("--paths", default="frames_dir,input_dir")
     ap.add_argument("--gpus", type=int, default=1,
@@ -97,7 +99,7 @@ def main():
     torch.save(synthetic.make_state_dict("johnson", 0), ck)
     frames = synthetic.make_frames(8, 1080, 1920, seed=300)
     res = {"frames": args.frames, "threads": args.threads, "frame_hw": [1080, 1920], "png_writer": args.png_writer,
-           "jpeg_reader": args.jpeg_reader,
+           "jpeg_reader": args.jpeg_reader, "jpeg_writer": args.jpeg_writer,
            "data": "synthetic 1080p frames (8 distinct, cycled)"}
     pool = ThreadPoolExecutor(args.threads)
     for ext in args.formats.split(","):
@@ -133,7 +135,8 @@ def main():
         res[ext] = dict(host)
         common = ["--model", ck, "--io_preset", "imagenet_255", "--dtype", "bf16", "--batch", "8", "--blend", "0.9",
                   "--smooth_alpha", "0.65", "--image_ext", ext, "--threads", str(args.threads),
-                  "--png_writer", args.png_writer, "--jpeg_reader", args.jpeg_reader]
+                  "--png_writer", args.png_writer, "--jpeg_reader", args.jpeg_reader,
+                  "--jpeg_writer", args.jpeg_writer]
         for path in args.paths.split(","):
             if path == "input_dir":
                 d_out = os.path.join(tmp, f"out_{ext}")
