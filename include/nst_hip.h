@@ -40,6 +40,18 @@ extern "C" {
 #define NST_ARCH_NST 1     /* transformer_net_nst.py:62-127 */
 #define NST_ARCH_RECONET 2 /* model.py:107-116 (frn=False, as pipeline.py:602 builds it) */
 #define NST_ARCH_RECONET_FRN 3 /* model.py:107-116 with frn=True: FRN + TLU (frn.py:7-78) */
+/* Torch7 fast-style nets (the *.t7 files pipeline.py:445-478, 583-596 runs through OpenCV DNN): ReflectionPad(40),
+ * zero-padded 9x9 / stride-2 convs, five residual blocks of two VALID 3x3 convs joined with the block input shaved
+ * by 2 px, two SpatialFullConvolution(3, s2, p1, adj1), 9x9 conv, Tanh, MulConstant.  Parameters by the NST_ARCH_NST
+ * names (down1.conv / down1.norm ... res5.conv2 / res5.norm2, up1, up2, final: the host matcher
+ * neuralstyletransferv1_amd/torch7.py emits them), plus "mul_constant" [1] and per norm layer "<norm>.eps" [1].
+ *   _IN: nn.InstanceNormalization (biased variance over the layer's own, shrinking map)
+ *   _BN: nn.SpatialBatchNormalization in eval mode: also "<norm>.running_mean" and "<norm>.running_var" [c]
+ * Output side for input H: 4*(h3 - 20), h1 = H + 80, h2 = (h1-1)/2 + 1, h3 = (h2-1)/2 + 1 (= H when H % 4 == 0);
+ * min(H, W) <= 40 is NST_E_SHAPE (the reflection needs pad < side).  Runs NST_DT_F32 / BF16 / F16 / F32S
+ * (NST_DT_F16M: NST_E_INVALID).  Frames go through NST_PRESET_TORCH7 only. */
+#define NST_ARCH_TORCH7_IN 4
+#define NST_ARCH_TORCH7_BN 5
 
 /* ---- compute dtypes ---- */
 #define NST_DT_F32 0  /* fp32 "parity" mode: exact-f32 MFMA (v_mfma_f32_16x16x4_f32) */
@@ -71,6 +83,14 @@ extern "C" {
 #define NST_PRESET_CAFFE_BGR 4
 #define NST_PRESET_RAW_255 5
 #define NST_PRESET_RAW_01 6
+/* The Torch7 nets' own pre / post arithmetic (pipeline.py:445-478; the NST_ARCH_TORCH7_* handles only, and the only
+ * preset they take besides NST_PRESET_NONE).  Input: the caffe_bgr encode, BGR255 - (103.939, 116.779, 123.68).
+ * Output: frame = trunc(clip(tanh(y) * mul_constant + mean, 0, 255)), BGR -> RGB; NST_IO_U8_NHWC gives the frame,
+ * NST_IO_F32_NCHW gives frame / 255 in RGB planes: what to_tensor(pil_out).clamp(0, 1) hands on at :1443, so it feeds
+ * nst_decode_resize_u8 / nst_blend_models_u8 / the region compositor as an NST_PRESET_RAW_01 source.  With
+ * NST_PRESET_NONE (NST_IO_F32_NCHW both sides) x is the mean-subtracted BGR blob and y = tanh(.) * mul_constant,
+ * what net.forward() returns at :466. */
+#define NST_PRESET_TORCH7 7
 
 typedef struct nst_handle nst_handle;
 typedef struct nst_lab nst_lab;

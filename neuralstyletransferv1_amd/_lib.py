@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("NST_HIP_LIB", os.path.join(_HERE, "libnst_hip.so"))
 
 NST_OK = 0
 NST_ARCH_JOHNSON, NST_ARCH_NST, NST_ARCH_RECONET, NST_ARCH_RECONET_FRN = 0, 1, 2, 3
+NST_ARCH_TORCH7_IN, NST_ARCH_TORCH7_BN = 4, 5  # the Torch7 fast-style nets, by norm kind (torch7.py)
 NST_DT_F32, NST_DT_BF16, NST_DT_F16, NST_DT_F32S, NST_DT_F16M = 0, 1, 2, 3, 4
 # kernel dtypes of the NST_DT_F16M split-precision layers (nst_op_desc.kernel_dtype)
 NST_KDT_SW_O32, NST_KDT_SW_O16, NST_KDT_SPLIT_O32, NST_KDT_SPLIT_O16, NST_KDT_SPLITO_O32 = 16, 17, 18, 19, 20
@@ -30,6 +31,9 @@ PRESETS = {
     "raw_255": 5,
     "raw_01": 6,
 }
+# the Torch7 nets' own pre / post arithmetic (include/nst_hip.h); not an --io_preset choice: torch7.Torch7Engine
+# applies it whatever preset its slot carries, as the reference's _torch7_forward_openv ignores io_preset
+NST_PRESET_TORCH7 = 7
 
 # every symbol include/nst_hip.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (

@@ -95,6 +95,8 @@ struct Layer {
   float* beta = nullptr;
   float eps = 1e-5f;  // InstanceNorm2d eps, or |FRN.eps|
   int frn = 0;        // statistics: mean / variance (InstanceNorm) or mean square (FRN, frn.py:71)
+  float2* bn_tab = nullptr;  // nn.SpatialBatchNormalization (NST_ARCH_TORCH7_BN): the constant {scale, shift} row
+                             // [coutp] that takes the place of the frames' InstanceNorm statistics
   bool prepad = false;  // image layer reading the pre-padded encoded input (conv_prep.hip)
   int kdt = 0;                   // the layer's arithmetic (NST_DT_* / NST_KDT_*): the handle's dtype except in NST_DT_F16M
   int in_esz = 2, out_esz = 2;   // activation element bytes it reads / writes
@@ -118,10 +120,13 @@ struct Op {
   int r_buf, r_norm, r_relu, relu_out;  // OP_RESADD; OP_CONV with res_buf >= 0: the residual join in the fill
   int res_buf = -1, res_out = -1;       // OP_CONV: residual stream r (joined into the fill) / where it is written
   int out_esz = 0;                      // OP_RESADD: element bytes of the stream it writes (0: the handle's)
+  int shave = 0;                        // OP_RESADD: r is 2 * shave larger per side than y and joined at (shave, shave)
+                                        // (nn.ShaveImage of the Torch7 nets' valid-conv blocks)
 };
 
 static int round_up(int v, int a) { return (v + a - 1) / a * a; }
 static bool is_reconet(int arch) { return arch == NST_ARCH_RECONET || arch == NST_ARCH_RECONET_FRN; }
+static bool is_torch7(int arch) { return arch == NST_ARCH_TORCH7_IN || arch == NST_ARCH_TORCH7_BN; }
 
 // x0_export (with fuse_res): block 1's conv1 also writes x_0 = ReLU(IN_2(C)) from its fill (only the
 // weight-stationary trunk kernel does), so block 2's join reads a stored x_0 like every later join
@@ -171,6 +176,20 @@ static void build_program(int arch, bool fuse_res, bool x0_export, std::vector<L
     L.push_back({"up1.conv", "up1.norm", 128, 64, 3, 1, AX_ZINSERT, 1, 0, true});
     L.push_back({"up2.conv", "up2.norm", 64, 32, 3, 1, AX_ZINSERT, 1, 0, true});
     L.push_back({"final", "", 32, 3, 9, 1, AX_ZERO, 4, 0, false});
+  } else if (is_torch7(arch)) {
+    // the Torch7 fast-style nets (pipeline.py:583-596 reads them with cv2.dnn.readNetFromTorch): the NST net's
+    // head and tail around a trunk of VALID 3x3 convs (pad 0: the map shrinks 2 px per conv)
+    L.push_back({"down1.conv", "down1.norm", 3, 32, 9, 1, AX_ZERO_PREREFLECT, 4, 40, false});
+    L.push_back({"down2.conv", "down2.norm", 32, 64, 3, 2, AX_ZERO, 1, 0, false});
+    L.push_back({"down3.conv", "down3.norm", 64, 128, 3, 2, AX_ZERO, 1, 0, false});
+    for (int r = 1; r <= 5; ++r) {
+      const std::string p = "res" + std::to_string(r);
+      L.push_back({p + ".conv1", p + ".norm1", 128, 128, 3, 1, AX_ZERO, 0, 0, false});
+      L.push_back({p + ".conv2", p + ".norm2", 128, 128, 3, 1, AX_ZERO, 0, 0, false});
+    }
+    L.push_back({"up1.conv", "up1.norm", 128, 64, 3, 1, AX_ZINSERT, 1, 0, true});
+    L.push_back({"up2.conv", "up2.norm", 64, 32, 3, 1, AX_ZINSERT, 1, 0, true});
+    L.push_back({"final", "", 32, 3, 9, 1, AX_ZERO, 4, 0, false});
   } else {
     // model.py:69-116 (FRN at the InstanceNorm's index, frn=True)
     L.push_back({"encoder.layers.0.layers.0.layers.1", "encoder.layers.0.layers.1", 3, 48, 9, 1, AX_REFLECT, 4, 0, false});
@@ -191,7 +210,23 @@ static void build_program(int arch, bool fuse_res, bool x0_export, std::vector<L
   conv(0, B_IMG, B_A, -1);
   conv(1, B_A, B_B, 0);
   conv(2, B_B, B_C, 1);
-  if (split_blocks > 0) {
+  if (is_torch7(arch)) {
+    // block k: y = norm2(conv2(ReLU(norm1(conv1(x_k))))) on a map 4 px smaller than x_k; x_{k+1} = y + x_k shaved by 2
+    // (nn.ConcatTable(branch, nn.ShaveImage(2)) + nn.CAddTable).  The join reads x_k at an offset, so it never
+    // runs in place: the stream alternates F / G (x_0 = ReLU(norm(C)) applied lazily, as in the unfused program)
+    int xbuf = B_C, xnorm = 2;
+    for (int r = 0; r < nres; ++r) {
+      const int l1 = 3 + 2 * r, l2 = 4 + 2 * r;
+      conv(l1, xbuf, B_D, xnorm);
+      conv(l2, B_D, B_E, l1);
+      const int xout = (r & 1) ? B_G : B_F;
+      resadd(l2, B_E, xout, xbuf, xnorm, 0);
+      P.back().shave = 2;
+      xbuf = xout;
+      xnorm = -1;
+    }
+    conv(u1, xbuf, B_A, -1);
+  } else if (split_blocks > 0) {
     // blocks 1..split_blocks unfused on fp32 activations: x_1 = IN(y) + ReLU(IN_2(C)) (fp32 in F when block 2 is
     // split too), x_2 = IN(y) + x_1; the last split block's sum is the fp16 stream in G; the later blocks are fused
     // from G (the first of them reads it as is)
@@ -269,6 +304,7 @@ struct nst_handle {
   // nst_set_stream_split: a batch runs as `split` sub-batches on internal streams forked from / joined to the
   // caller's, so one sub-batch's launch gaps and kernel tails are filled by another's kernels
   int split = 1;
+  float t7_mul = 0.f;  // nn.MulConstant's constant_scalar (NST_ARCH_TORCH7_*)
   hipStream_t sub[NST_MAX_STREAM_SPLIT] = {};
   hipEvent_t fork = nullptr, join[NST_MAX_STREAM_SPLIT] = {};
 };
@@ -653,6 +689,7 @@ bool layer_input_ok(const LayerDef& d, int L) {
   if (d.axis_mode == AX_REFLECT) return L > d.pad;
   if (d.axis_mode == AX_REFLECT_UP2) return 2 * L > d.pad;
   if (d.axis_mode == AX_ZERO_PREREFLECT) return L > d.pre;
+  if (d.axis_mode == AX_ZERO) return L + 2 * d.pad >= d.ks;  // a valid conv (pad 0) needs a whole window
   return L >= 1;
 }
 
@@ -670,6 +707,7 @@ struct Plan {
   size_t seg_bytes = 0;
   size_t off_buf[NBUF], off_partial, off_seg, off_stats, off_pre = 0;
   size_t pre_bytes = 0;
+  size_t off_tail = 0, tail_bytes = 0;  // Torch7 nets: the output conv's raw fp32 planes, read by the tail kernel
 };
 
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
@@ -760,6 +798,11 @@ Plan make_plan(const nst_handle* h, int n, int H, int W) {
         if (sb > P.seg_bytes) P.seg_bytes = sb;
       }
     } else {
+      if (bh[op.r_buf] != bh[op.src] + 2 * op.shave || bw[op.r_buf] != bw[op.src] + 2 * op.shave) {
+        P.err = "internal: residual join of a " + std::to_string(bh[op.src]) + "x" + std::to_string(bw[op.src]) +
+                " map with a " + std::to_string(bh[op.r_buf]) + "x" + std::to_string(bw[op.r_buf]) + " stream";
+        return P;
+      }
       P.ih[i] = P.oh[i] = bh[op.src];
       P.iw[i] = P.ow[i] = bw[op.src];
       P.in_esz[i] = be[op.src];
@@ -780,6 +823,9 @@ Plan make_plan(const nst_handle* h, int n, int H, int W) {
   off += align256(P.seg_bytes);
   P.off_pre = off;
   off += align256(P.pre_bytes);
+  if (is_torch7(h->arch)) P.tail_bytes = (size_t)n * 3 * P.out_h * P.out_w * 4;
+  P.off_tail = off;
+  off += align256(P.tail_bytes);
   P.off_stats = off;
   for (const Layer& Ly : h->layers) off += align256((size_t)n * Ly.coutp * 8);
   P.ws_bytes = off;
@@ -817,6 +863,7 @@ bool preset_consts(int preset, PresetConsts& c) {
       }
       return true;
     case NST_PRESET_CAFFE_BGR:
+    case NST_PRESET_TORCH7:  // the same encode; its output side is the Torch7 tail kernel, not these constants
       for (int i = 0; i < 3; ++i) {
         c.ea[i] = 255.f; c.eb[i] = caffe[i]; c.eperm[i] = 2 - i; c.dr[i] = 255.f; c.dperm[i] = 2 - i;
       }
@@ -958,7 +1005,7 @@ int nst_create(int arch, const nst_param* params, int n_params, int compute_dtyp
 
 int nst_create_ex(int arch, const nst_param* params, int n_params, int compute_dtype, int device,
                   unsigned flags, nst_handle** out) {
-  if (!out || arch < 0 || arch > 3 || (compute_dtype != NST_DT_F32 && compute_dtype != NST_DT_BF16 && compute_dtype != NST_DT_F16 &&
+  if (!out || arch < 0 || arch > NST_ARCH_TORCH7_BN || (compute_dtype != NST_DT_F32 && compute_dtype != NST_DT_BF16 && compute_dtype != NST_DT_F16 &&
                                            compute_dtype != NST_DT_F32S && compute_dtype != NST_DT_F16M) ||
       (flags & ~(unsigned)NST_KSEL_ALL) != 0) {
     set_error("nst_create: invalid arguments");
@@ -968,6 +1015,10 @@ int nst_create_ex(int arch, const nst_param* params, int n_params, int compute_d
   // residual blocks on the split-operand kernel: the first (tests/precision_study.py: live max 0.958 LSB on the
   // bench frames; 1,114 frames/s), or the first two with NST_KSEL_F16M_TWO_BLOCKS (0.920 LSB; 1,014 frames/s)
   const int split_blocks = !f16m ? 0 : ((flags & NST_KSEL_F16M_TWO_BLOCKS) ? 2 : 1);
+  if (f16m && is_torch7(arch)) {
+    set_error("nst_create: NST_DT_F16M is not built for the Torch7 nets (use NST_DT_F32S or NST_DT_F32)");
+    return NST_E_INVALID;
+  }
   if (f16m && (is_reconet(arch) || (flags & (NST_KSEL_UNFUSED_RESIDUAL | NST_KSEL_NO_WS9 | NST_KSEL_NO_WS2 | NST_KSEL_NO_PREPAD)))) {
     set_error("nst_create: NST_DT_F16M is built for the Johnson / NST nets with the default kernel selection");
     return NST_E_INVALID;
@@ -1001,7 +1052,8 @@ int nst_create_ex(int arch, const nst_param* params, int n_params, int compute_d
   auto* h = new nst_handle();
   h->arch = arch; h->dtype = compute_dtype; h->device = device;
   std::vector<LayerDef> defs;
-  const bool fuse_res = (flags & NST_KSEL_UNFUSED_RESIDUAL) == 0;
+  // the Torch7 nets' shaved join is its own kernel (t7_ops.hip): their program has no fused form
+  const bool fuse_res = (flags & NST_KSEL_UNFUSED_RESIDUAL) == 0 && !is_torch7(arch);
   build_program(arch, fuse_res, fuse_res, defs, h->prog, split_blocks);
   // layers whose fill joins the residual stream run the VAR_RES instantiation
   std::vector<int> res_layer(defs.size(), 0);
@@ -1067,7 +1119,8 @@ int nst_create_ex(int arch, const nst_param* params, int n_params, int compute_d
     }
     // residual-trunk convs (128 -> 128, 3x3): weight-stationary kernel (conv_wstat.hip); ReCoNet's
     // trunk is 192 channels and its join has a ReLU after the sum, so it never matches
-    if (!up && !final_layer && !image_in && d.ks == 3 && d.stride == 1 && !is_reconet(arch) &&
+    // (nor do the Torch7 nets' valid convs: that kernel is built around a same-size map)
+    if (!up && !final_layer && !image_in && d.ks == 3 && d.stride == 1 && !is_reconet(arch) && !is_torch7(arch) &&
         !(flags & NST_KSEL_NO_WSTAT))
       modes.push_back(MODE_WSTAT);
     // stride-2 down-convs: weight-stationary kernel (conv_ws2.hip) where compiled
@@ -1113,6 +1166,25 @@ int nst_create_ex(int arch, const nst_param* params, int n_params, int compute_d
       if ((rc = get(d.norm + ".bias", d.cout, &bt)) != NST_OK) break;
     }
     std::vector<float> b_fold, bt_fold;
+    if (is_torch7(arch) && !final_layer) {
+      // the file's own eps; SpatialBatchNormalization in eval mode is the constant affine map
+      //   y = x * scale + shift, scale = weight / sqrt(running_var + eps), shift = bias - running_mean * scale
+      const float* e = nullptr;
+      if ((rc = get(d.norm + ".eps", 1, &e)) != NST_OK) break;
+      if (!(e[0] >= 0.f)) { set_error("checkpoint tensor " + d.norm + ".eps is negative or NaN"); rc = NST_E_PARAM; break; }
+      Ly.eps = e[0];
+      if (arch == NST_ARCH_TORCH7_BN) {
+        const float *rm = nullptr, *rv = nullptr;
+        if ((rc = get(d.norm + ".running_mean", d.cout, &rm)) != NST_OK) break;
+        if ((rc = get(d.norm + ".running_var", d.cout, &rv)) != NST_OK) break;
+        std::vector<float2> tab(Ly.coutp, make_float2(0.f, 0.f));
+        for (int c = 0; c < d.cout; ++c) {
+          const double scale = (double)gm[c] / std::sqrt((double)rv[c] + (double)Ly.eps);
+          tab[c] = make_float2((float)scale, (float)((double)bt[c] - (double)rm[c] * scale));
+        }
+        if ((rc = upload(tab.data(), tab.size() * sizeof(float2), (void**)&Ly.bn_tab)) != NST_OK) break;
+      }
+    }
     if (arch == NST_ARCH_RECONET_FRN) {
       if ((rc = frn_layer(get, (int)li, d, W, b, bt, b_fold, bt_fold, Ly.eps)) != NST_OK) break;
       b = b_fold.data();
@@ -1146,7 +1218,7 @@ int nst_create_ex(int arch, const nst_param* params, int n_params, int compute_d
       break;
     }
     if (Ly.prepad && !f32_storage(compute_dtype) && !(flags & NST_KSEL_NO_FOLD)) {
-      for (int pr = 1; pr < 8 && rc == NST_OK; ++pr) {
+      for (int pr = 1; pr < NST_PRESET_TORCH7 && rc == NST_OK; ++pr) {
         std::vector<float> Wf, bfo;
         if (!fold_first_layer(d, W, b, pr, Wf, bfo)) continue;
         std::vector<float> pk = Ly.mode == MODE_WS9 ? pack_ws9_weights(*Ly.k_main, d, Wf.data())
@@ -1165,7 +1237,7 @@ int nst_create_ex(int arch, const nst_param* params, int n_params, int compute_d
         !(flags & (NST_KSEL_NO_FOLD | NST_KSEL_NO_WS9 | NST_KSEL_NO_PREPAD))) {
       const ConvKernelInfo* kf = find_conv_kernel(NST_KDT_SW_O32, MODE_WS9, d.ks, d.stride, 4, Ly.coutp, IN_ACT, OUT_ACT, 0, no_pers);
       if (kf && kf->out_esz == Ly.out_esz && kf->bn == Ly.coutp) {
-        for (int pr = 1; pr < 8 && rc == NST_OK; ++pr) {
+        for (int pr = 1; pr < NST_PRESET_TORCH7 && rc == NST_OK; ++pr) {
           std::vector<float> Wf, bfo;
           if (!fold_first_layer(d, W, b, pr, Wf, bfo)) continue;
           if ((rc = upload_weights(NST_DT_F16, split_weight_frags(*kf, pack_ws9_weights(*kf, d, Wf.data())), &Ly.wpk_fold[pr])) != NST_OK)
@@ -1196,6 +1268,10 @@ int nst_create_ex(int arch, const nst_param* params, int n_params, int compute_d
       if ((rc = upload(btp.data(), btp.size() * 4, (void**)&Ly.beta)) != NST_OK) break;
     }
     h->layers.push_back(Ly);
+  }
+  if (rc == NST_OK && is_torch7(arch)) {
+    const float* mc = nullptr;
+    if ((rc = get("mul_constant", 1, &mc)) == NST_OK) h->t7_mul = mc[0];
   }
   if (rc != NST_OK) {
     nst_destroy(h);
@@ -1232,6 +1308,7 @@ void nst_destroy(nst_handle* h) {
     if (Ly.bias) (void)hipFree(Ly.bias);
     if (Ly.gamma) (void)hipFree(Ly.gamma);
     if (Ly.beta) (void)hipFree(Ly.beta);
+    if (Ly.bn_tab) (void)hipFree(Ly.bn_tab);
     for (int pr = 0; pr < 8; ++pr) {
       if (Ly.wpk_fold[pr]) (void)hipFree(Ly.wpk_fold[pr]);
       if (Ly.bias_fold[pr]) (void)hipFree(Ly.bias_fold[pr]);
@@ -1308,6 +1385,11 @@ int forward_impl(nst_handle* h, const void* x, int x_fmt, int n, int in_h, int i
     set_error("nst_forward: uint8 frames need an io_preset");
     return NST_E_INVALID;
   }
+  const bool t7 = is_torch7(h->arch);
+  if (t7 ? (preset != NST_PRESET_NONE && preset != NST_PRESET_TORCH7) : preset == NST_PRESET_TORCH7) {
+    set_error("nst_forward: NST_PRESET_TORCH7 is the Torch7 nets' own pre / post arithmetic, and the only preset they take");
+    return NST_E_INVALID;
+  }
   Plan P = make_plan(h, n, in_h, in_w);
   if (!P.ok) { set_error(P.err); return NST_E_SHAPE; }
   if (y_fmt == NST_IO_U8_NHWC && (P.out_h != in_h || P.out_w != in_w)) {
@@ -1343,7 +1425,10 @@ int forward_impl(nst_handle* h, const void* x, int x_fmt, int n, int in_h, int i
       const int hw = P.oh[i] * P.ow[i];
       // element formats of y / r / out: all the handle's, all fp32 (NST_DT_F16M's first join), or fp32 -> fp16
       const int rdt = P.out_esz[i] == 4 ? NST_DT_F32 : h->dtype;
-      hipError_t e = (P.in_esz[i] == 4 && P.res_esz[i] == 4 && P.out_esz[i] == 2)
+      hipError_t e = op.shave > 0
+                         ? launch_residual_shave(rdt, bufs[op.src], tab(op.layer), bufs[op.r_buf], tab(op.r_norm), op.r_relu,
+                                                 bufs[op.dst], n, P.oh[i], P.ow[i], op.shave, Ly.coutp, st)
+                     : (P.in_esz[i] == 4 && P.res_esz[i] == 4 && P.out_esz[i] == 2)
                          ? launch_residual_f32_to_f16(bufs[op.src], tab(op.layer), bufs[op.r_buf], tab(op.r_norm),
                                                       op.r_relu, op.relu_out, bufs[op.dst], n, hw, Ly.coutp, st)
                          : launch_residual(rdt, bufs[op.src], tab(op.layer), bufs[op.r_buf], tab(op.r_norm), op.r_relu,
@@ -1357,7 +1442,7 @@ int forward_impl(nst_handle* h, const void* x, int x_fmt, int n, int in_h, int i
     const bool image_in = op.src == B_IMG, final_out = op.dst == B_OUT;
     const ConvKernelInfo* k = Ly.k_main;
     if (image_in && x_fmt == NST_IO_F32_NCHW) k = Ly.k_alt;
-    if (final_out && y_fmt == NST_IO_F32_NCHW) k = Ly.k_alt;
+    if (final_out && (y_fmt == NST_IO_F32_NCHW || t7)) k = Ly.k_alt;  // Torch7: raw fp32 planes for the tail kernel
     // uint8 frames through a first layer with this preset folded in: stage the raw bytes (exact operand)
     const bool fold = image_in && x_fmt == NST_IO_U8_NHWC && preset >= 0 && preset < 8 && Ly.wpk_fold[preset] != nullptr &&
                       (Ly.prepad || Ly.k_u8fold);
@@ -1418,7 +1503,7 @@ int forward_impl(nst_handle* h, const void* x, int x_fmt, int n, int in_h, int i
     p.dec_tanh = (is_reconet(h->arch) && final_out) ? 1 : 0;
     p.wpk = fold ? Ly.wpk_fold[preset] : Ly.wpk;
     p.bias = fold ? Ly.bias_fold[preset] : Ly.bias;
-    if (mode == MODE_XSHIFT && final_out && y_fmt == NST_IO_U8_NHWC && pc.dperm[0] == 2) {
+    if (mode == MODE_XSHIFT && final_out && y_fmt == NST_IO_U8_NHWC && pc.dperm[0] == 2 && !t7) {
       p.wpk = Ly.wpk_rev;  // decode channel c from model channel 2-c (caffe_bgr)
       p.bias = Ly.bias_rev;
     }
@@ -1428,7 +1513,7 @@ int forward_impl(nst_handle* h, const void* x, int x_fmt, int n, int in_h, int i
     p.ow = P.ow[i];
     p.crop_y = (P.ch[i] - P.oh[i]) / 2;
     p.crop_x = (P.cw[i] - P.ow[i]) / 2;
-    p.out = final_out ? y : bufs[op.dst];
+    p.out = final_out ? (t7 ? (void*)(ws + P.off_tail) : y) : bufs[op.dst];
     p.cout_real = Ly.d.cout;
     p.cout_stride = Ly.coutp;
     tile_grid(*k, p.hs, p.ws, p.oh, p.ow, &p.tiles_x, &p.tiles_y);
@@ -1485,7 +1570,15 @@ int forward_impl(nst_handle* h, const void* x, int x_fmt, int n, int in_h, int i
       h->recs.push_back(rec);
     }
     if (e != hipSuccess) { set_error("conv " + Ly.d.conv + " launch: " + hipGetErrorString(e)); return NST_E_HIP; }
-    if (!final_out) {
+    if (final_out && t7) {
+      const int tmode = preset == NST_PRESET_NONE ? 0 : (y_fmt == NST_IO_F32_NCHW ? 1 : 2);
+      e = launch_t7_tail((const float*)(ws + P.off_tail), n, P.out_h, P.out_w, h->t7_mul, tmode, y, st);
+      if (e != hipSuccess) { set_error(std::string("torch7 tail launch: ") + hipGetErrorString(e)); return NST_E_HIP; }
+    }
+    if (!final_out && Ly.bn_tab) {
+      e = launch_norm_table_fill(Ly.bn_tab, n, Ly.coutp, tab(op.layer), st);
+      if (e != hipSuccess) { set_error(std::string("norm table launch: ") + hipGetErrorString(e)); return NST_E_HIP; }
+    } else if (!final_out) {
       e = launch_in_finalize(partial, n, p.tiles_x * p.tiles_y * k->part_rows, Ly.coutp, (double)p.hconv * (double)p.wconv,
                              Ly.gamma, Ly.beta, Ly.eps, Ly.frn, tab(op.layer), ws + P.off_seg, st);
       if (e == hipSuccess && h->range_flag)

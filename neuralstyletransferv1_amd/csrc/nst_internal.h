@@ -193,6 +193,19 @@ hipError_t launch_residual(int dtype, const void* y, const float2* ys, const voi
 // output, normalised + ReLU'd as rs / r_relu say) -> the fp16 stream out = rr + (y * ys.x + ys.y) [+ ReLU]
 hipError_t launch_residual_f32_to_f16(const void* y, const float2* ys, const void* r, const float2* rs, int r_relu,
                                       int relu_out, void* out, int n, int hw, int c, hipStream_t st);
+// ---- Torch7 fast-style nets (t7_ops.hip) ----
+// nn.ShaveImage(s) + nn.CAddTable: out[n][y][x] = y[n][y][x] * ys + r'[n][y + s][x + s], r' = r or ReLU(r * rs) (the
+// first block's input, never materialised); y / out [n][oh][ow][c], r [n][oh + 2s][ow + 2s][c], NHWC in the compute
+// dtype, the arithmetic and roundings of launch_residual.  out must not alias r
+hipError_t launch_residual_shave(int dtype, const void* y, const float2* ys, const void* r, const float2* rs, int r_relu,
+                                 void* out, int n, int oh, int ow, int shave, int c, hipStream_t st);
+// nn.SpatialBatchNormalization (eval): the layer's constant {scale, shift} row tab[c] into the n frames' rows of its
+// norm table, where an InstanceNorm layer's finalize writes the frames' statistics
+hipError_t launch_norm_table_fill(const float2* tab, int n, int c, float2* out, hipStream_t st);
+// the tail over the output conv's raw fp32 NCHW planes t (BGR): mode 0 -> fp32 NCHW tanh(t) * mul (nn.Tanh +
+// nn.MulConstant); 1 -> fp32 NCHW RGB planes frame / 255; 2 -> u8 NHWC RGB frame, with
+// frame = trunc(clip(tanh(t) * mul + caffe mean, 0, 255)) (pipeline.py:466-474)
+hipError_t launch_t7_tail(const float* t, int n, int h, int w, float mul, int mode, void* out, hipStream_t st);
 hipError_t launch_decode_resize_u8(const float* y, int n, int h, int w, const float* p,
                                    const float* q, const float* r, const float* s, const int* perm,
                                    uint8_t* out, int oh, int ow, hipStream_t st);

@@ -259,6 +259,7 @@ class StylizationNet(nn.Module):
     """Base of the drop-in TransformerNet / ReCoNet modules (parameters = containers)."""
 
     ARCH: int = -1
+    ENGINE_CLS = Engine  # the handle class engine() builds (torch7.Torch7Net: its own pre / post arithmetic)
 
     def __init__(self):
         super().__init__()
@@ -274,13 +275,20 @@ class StylizationNet(nn.Module):
         self.kernel_select = frozenset()
         self._engines: Dict[Tuple[str, int, str, int], Tuple[tuple, Engine]] = {}
 
+    def _engine_state(self) -> Dict[str, torch.Tensor]:
+        """The tensors the handle packs, by the engine's parameter names."""
+        return self.state_dict()
+
+    def _module_device(self) -> torch.device:
+        return next(self.parameters()).device
+
     def _param_key(self) -> tuple:
-        return tuple((p.data_ptr(), p._version) for p in self.state_dict().values())
+        return tuple((p.data_ptr(), p._version) for p in self._engine_state().values())
 
     def engine(self, device: Optional[torch.device] = None, dtype: Optional[str] = None) -> Engine:
         """Packed handle for the current parameters (re-packed after load_state_dict / in-place edits)."""
         if device is None:
-            device = next(self.parameters()).device
+            device = self._module_device()
             if device.type != "cuda":
                 raise NstError("move the module (or pass a device) to an MI355X first: there is no CPU path")
         device = torch.device(device)
@@ -299,7 +307,7 @@ class StylizationNet(nn.Module):
         hit = self._engines.get(key)
         if hit is not None and hit[0] == pk:
             return hit[1]
-        eng = Engine(self.ARCH, self.state_dict(), dtype, device, flags)
+        eng = self.ENGINE_CLS(self.ARCH, self._engine_state(), dtype, device, flags)
         self._engines[key] = (pk, eng)
         return eng
 

@@ -28,8 +28,11 @@ The flow-guided EMA (--flow_ema with --flow_method dis, the default, or farnebac
 --flow_downscale factor, floored like the reference's (W0 // ds, H0 // ds)) and the motion-adaptive blend
 (--motion_blend, :2072-2086) run on the GPU (temporal.py).
 
-Not built (rejected with a clear message if requested): Magenta (TF-Hub) and Torch7
-(OpenCV DNN) backends.
+Torch7 .t7 networks (--model_type torch7, or a .t7 file in any slot; pipeline.py:445-478, 583-596 runs them
+through OpenCV DNN on the CPU) run on the engine (torch7.py); the half-size retry after a crashed OpenCV forward
+(:1432-1442) is not imitated.
+
+Not built (rejected with a clear message if requested): the Magenta (TF-Hub) backend.
 """
 from __future__ import annotations
 
@@ -195,15 +198,21 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def slot_model_type(args, s: str) -> str:
+    """Back end of slot b..h: its own --model_<s>_type, else torch7 for a .t7 file, else slot A's (pipeline.py:631-632)."""
+    p = getattr(args, f"model_{s}", None)
+    auto = "torch7" if p and Path(str(p)).suffix.lower() == ".t7" else args.model_type
+    return getattr(args, f"model_{s}_type", None) or auto
+
+
 def reject_out_of_scope(args) -> None:
     bad = []
-    if args.model_type in ("magenta", "torch7"):
+    if args.model_type == "magenta":
         bad.append(f"--model_type {args.model_type}")
     for s in SLOTS:
-        if getattr(args, f"model_{s}") and (getattr(args, f"model_{s}_type") in ("magenta", "torch7")
-                                             or str(getattr(args, f"model_{s}")).lower() in ("magenta",)
-                                             or str(getattr(args, f"model_{s}")).endswith(".t7")):
-            bad.append(f"--model_{s} (magenta/torch7)")
+        if getattr(args, f"model_{s}") and (getattr(args, f"model_{s}_type") == "magenta"
+                                             or str(getattr(args, f"model_{s}")).lower() in ("magenta",)):
+            bad.append(f"--model_{s} (magenta)")
     if args.device != "cuda":
         bad.append(f"--device {args.device} (this engine runs on MI355X only; there is no CPU path)")
     if bad:
@@ -373,9 +382,38 @@ def _load_checkpoint_compat(model, ckpt_path: str) -> None:
     _log(f">> load_state_dict: missing={len(missing)} unexpected={len(unexpected)}")
 
 
+_T7_LOADED: Dict[str, tuple] = {}  # resolved path -> (norm kind, parameters): prepare's check, reused by load_model
+
+
+def load_torch7_or_exit(path: str, slot: str = "A"):
+    """Read a Torch7 .t7 file and match it against the published fast-style architecture (host only).  A file that
+    is missing, unreadable or not that architecture ends the run with code 2, as pipeline.py:594-596 does."""
+    from ._lib import NstError
+    from .torch7 import load_t7
+    key = str(Path(path).resolve())
+    if key not in _T7_LOADED:
+        try:
+            _T7_LOADED[key] = load_t7(key)
+        except NstError as e:
+            tag = "[torch7]" if slot == "A" else f"[torch7][{slot}]"
+            _log(f"{tag}[ERROR] Could not load .t7 network from {path}: {e}")
+            sys.exit(2)
+    return _T7_LOADED[key]
+
+
 def load_model(path: str, model_type: str, device, dtype: str, slot: str = "A", auto_nst: bool = True):
     """Model construction + load (pipeline.py:597-619; slots B..H always use the Johnson class for
     type transformer, :651-661 — kept)."""
+    if model_type == "torch7":  # pipeline.py:583-596: the .t7 file on the engine instead of OpenCV DNN on the CPU
+        from .torch7 import Torch7Net
+        kind, params = load_torch7_or_exit(path, slot)
+        model = Torch7Net(kind, params).to(device).eval()
+        if dtype == "fp16m":  # as for ReCoNet: the split-precision head is built for the Johnson / NST nets
+            _log("[backend] fp16m is built for the Johnson / NST nets; the Torch7 net runs fp32s (the same +-1 LSB bar)")
+            dtype = "fp32s"
+        model.compute_dtype = dtype
+        _log(f"[backend] {slot}: type={model_type} path={path} device={device} arch=torch7_{kind} dtype={dtype}")
+        return model, "torch7"
     if model_type == "reconet":
         from .model import ReCoNet
         model, arch = ReCoNet(), "reconet"
@@ -506,16 +544,18 @@ def style_frames(args, frames_dir: Optional[Path], model_path, output_prefix: st
     if arch_a == "nst" and io_preset in ("auto", "raw_255", "imagenet_255"):  # pipeline.py:610-614
         _log(f"[model] Auto-switching io_preset from '{io_preset}' to 'raw_01' for NST_Train model")
         io_preset = "raw_01"
-    slots.append((model_a, io_preset))
+    # a Torch7 slot ignores its io_preset (pipeline.py:445-478) and hands on out01 = frame / 255 (:1443): toward the
+    # fit, the blends, the regions and the temporal stage it is a raw_01 source (torch7.Torch7Engine)
+    slots.append((model_a, "raw_01" if arch_a == "torch7" else io_preset))
     slot_letters.append(0)
     for li, s in enumerate(SLOTS, start=1):
         p = getattr(args, f"model_{s}", None)
         if not p:
             continue
-        t = getattr(args, f"model_{s}_type", None) or args.model_type
+        t = slot_model_type(args, s)
         ip = getattr(args, f"io_preset_{s}", None) or io_preset
-        m, _ = load_model(p, t, dev, args.dtype, s.upper(), auto_nst=False)
-        slots.append((m, ip))
+        m, arch_s = load_model(p, t, dev, args.dtype, s.upper(), auto_nst=False)
+        slots.append((m, "raw_01" if arch_s == "torch7" else ip))
         slot_letters.append(li)
     # pipeline.py:1519-1520: the standard path blends only when one of B, C, D is in use, and counts models as
     # 1 + B + C + D (slots E..H join the outputs list but the weights cover the first num_models of it)
@@ -1124,6 +1164,12 @@ def prepare(args):
         args.io_preset = IO_PRESETS_AUTO.get(args.model_type, "imagenet_01")
         _log(f"[auto] io_preset resolved to '{args.io_preset}' for backend '{args.model_type}'")
     reject_out_of_scope(args)
+    # Torch7 slots: read and match the files now, before anything is staged (exit 2 on a bad one, :594-596, :648-650)
+    if args.model_type == "torch7":
+        load_torch7_or_exit(str(model_path), "A")
+    for s in SLOTS:
+        if getattr(args, f"model_{s}", None) and slot_model_type(args, s) == "torch7":
+            load_torch7_or_exit(str(getattr(args, f"model_{s}")), s.upper())
     save_map: Dict[int, str] = {}
     base_work = Path(args.work_dir).resolve()
     if synthetic:

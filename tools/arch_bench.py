@@ -1,18 +1,35 @@
-"""Secondary timings: the three architectures (and ReCoNet(frn=True)) at 1080p, batch 8, bf16 (frames/s per GPU, HBM-resident
-uint8 frames, same step as bench.py).  Not part of the bench contract; numbers quoted in DESIGN.md."""
+"""Secondary timings: the three architectures (and ReCoNet(frn=True), and the Torch7 .t7 nets of both norm kinds) at
+1080p, batch 8, bf16 (frames/s per GPU, HBM-resident uint8 frames, same step as bench.py).  Not part of the bench
+contract; numbers quoted in DESIGN.md.  `python tools/arch_bench.py [arch ...]` runs only the named ones."""
 import os, sys, time
 import torch
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from neuralstyletransferv1_amd import synthetic
+
+
+def build(arch):
+    if arch.startswith("torch7_"):  # seeded parameters of the published architecture (tests/t7_write.py)
+        import t7_write
+        from neuralstyletransferv1_amd.torch7 import Torch7Net
+        kind = arch[len("torch7_"):]
+        return Torch7Net(kind, t7_write.make_params(kind, 0, 0.5))
+    m = synthetic.build_module(arch)
+    m.load_state_dict(synthetic.make_state_dict(arch, 0))
+    return m
+
 
 dev = torch.device("cuda", 0)
 frames = torch.from_numpy(synthetic.make_frames(8, 1080, 1920, seed=5)).to(dev)
 runs = [("johnson", "imagenet_255", ()), ("nst", "raw_01", ()), ("reconet", "tanh", ()), ("reconet_frn", "tanh", ()),
-        ("reconet", "tanh", ("no_persistent",))]  # ReCoNet's trunk on the register-streamed kernel, for comparison
+        ("reconet", "tanh", ("no_persistent",)),  # ReCoNet's trunk on the register-streamed kernel, for comparison
+        ("torch7_in", "caffe_bgr", ()), ("torch7_bn", "caffe_bgr", ())]  # valid-conv trunk on the generic kernels
+only = set(sys.argv[1:])
 for arch, preset, ksel in runs:
-    m = synthetic.build_module(arch)
-    m.load_state_dict(synthetic.make_state_dict(arch, 0))
-    m = m.to(dev).eval()
+    if only and arch not in only:
+        continue
+    m = build(arch).to(dev).eval()
     m.compute_dtype = "bf16"
     m.kernel_select = frozenset(ksel)
     for _ in range(3):
