@@ -391,10 +391,22 @@ int nst_adam_step(float* x, const float* grad, float* m, float* v, int c, int hw
  * names without the "module." prefix (sky_swap.py:150 strips it), e.g. "backbone.layer3.22.conv2.weight",
  * "aspp.global_avg_pool.1.weight", "decoder.last_conv.8.bias"; running_mean / running_var are used,
  * num_batches_tracked is ignored.  NHWC activations in the compute dtype, fp32 accumulation; compute_dtype
- * NST_DT_F32S keeps fp32 activations and splits every conv's operands into fp16 pairs (the split-fp16 GEMM). */
+ * NST_DT_F32S keeps fp32 activations and splits every conv's operands into fp16 pairs (the split-fp16 GEMM).
+ *
+ * nst_seg_create_ex picks the backbone.  NST_SEG_RESNET101: the network above (what nst_seg_create builds).
+ * NST_SEG_DRN_D54: backbone 'drn' = DRN-D-54 (modeling/backbone/drn.py:102-234, :386-387), for which deeplab.py:13-14
+ * forces output stride 8: a 7x7 3->16, 3x3 16->16 and 3x3/2 16->32 head at full input resolution (direct
+ * convolutions, fp32 accumulation, preprocess fused), bottleneck layers 3..6 (3, 4, 6, 3 blocks; strides 2, 2, 1, 1;
+ * dilations 1, 1, 2, 4), two conv layers 2048->512->512, ASPP on 512 channels with dilations 1, 12, 24, 36, the same
+ * decoder on layer3's 256 channels at 1/4.  Names e.g. "backbone.layer0.0.weight", "backbone.layer6.2.conv2.weight",
+ * "backbone.layer7.1.running_var".  Every other nst_seg_* entry serves either handle. */
+#define NST_SEG_RESNET101 0
+#define NST_SEG_DRN_D54 1
 typedef struct nst_seg nst_seg;
 int nst_seg_create(const nst_param* params, int n_params, int num_classes, int compute_dtype, int device,
                    nst_seg** out);
+int nst_seg_create_ex(const nst_param* params, int n_params, int num_classes, int compute_dtype, int device,
+                      int backbone, nst_seg** out);
 void nst_seg_destroy(nst_seg* s);
 int nst_seg_num_classes(const nst_seg* s);
 int nst_seg_workspace_bytes(const nst_seg* s, int n, int h, int w, size_t* out);

@@ -22,6 +22,7 @@ NST_DT_F32, NST_DT_BF16, NST_DT_F16, NST_DT_F32S, NST_DT_F16M = 0, 1, 2, 3, 4
 NST_KDT_SW_O32, NST_KDT_SW_O16, NST_KDT_SPLIT_O32, NST_KDT_SPLIT_O16, NST_KDT_SPLITO_O32 = 16, 17, 18, 19, 20
 NST_VGG_GENERIC_ONLY = 0x1
 NST_IO_F32_NCHW, NST_IO_U8_NHWC = 0, 1
+NST_SEG_RESNET101, NST_SEG_DRN_D54 = 0, 1  # nst_seg_create_ex backbones
 PRESETS = {
     "none": 0,
     "tanh": 1,
@@ -44,7 +45,7 @@ EXPORTED_SYMBOLS = (
     "nst_mask_feather", "nst_create_ex", "nst_num_ops", "nst_op_describe", "nst_forward_capture",
     "nst_gram_workspace_bytes", "nst_vgg_create", "nst_vgg_create_ex", "nst_vgg_destroy", "nst_gatys_buffer_bytes", "nst_vgg_features",
     "nst_gatys_targets", "nst_gatys_grad", "nst_adam_step", "nst_gatys_grad_capture",
-    "nst_seg_create", "nst_seg_destroy", "nst_seg_num_classes", "nst_seg_workspace_bytes", "nst_seg_forward",
+    "nst_seg_create", "nst_seg_create_ex", "nst_seg_destroy", "nst_seg_num_classes", "nst_seg_workspace_bytes", "nst_seg_forward",
     "nst_seg_mask_scratch_bytes", "nst_seg_mask", "nst_resize_create", "nst_resize_destroy",
     "nst_resize_scratch_bytes", "nst_resize_u8", "nst_blend_mask8_u8",
     "nst_region_masks", "nst_region_feather", "nst_region_rotate", "nst_region_bbox", "nst_region_scratch_floats",
@@ -172,6 +173,7 @@ def lib() -> ctypes.CDLL:
         L.nst_destroy.argtypes = [vp]
         L.nst_destroy.restype = None
         L.nst_seg_create.argtypes = [ctypes.POINTER(NstParam), i, i, i, i, ctypes.POINTER(vp)]
+        L.nst_seg_create_ex.argtypes = [ctypes.POINTER(NstParam), i, i, i, i, i, ctypes.POINTER(vp)]
         L.nst_seg_destroy.argtypes = [vp]
         L.nst_seg_destroy.restype = None
         L.nst_seg_num_classes.argtypes = [vp]
@@ -264,7 +266,7 @@ def lib() -> ctypes.CDLL:
         L.nst_num_layers.restype = i
         L.nst_layer_name.argtypes = [vp, i]
         L.nst_layer_name.restype = ctypes.c_char_p
-        for name in ("nst_seg_create", "nst_seg_num_classes", "nst_seg_workspace_bytes", "nst_seg_forward",
+        for name in ("nst_seg_create", "nst_seg_create_ex", "nst_seg_num_classes", "nst_seg_workspace_bytes", "nst_seg_forward",
                      "nst_seg_mask_scratch_bytes", "nst_seg_mask", "nst_resize_create", "nst_resize_scratch_bytes",
                      "nst_resize_u8", "nst_vgg_create", "nst_vgg_create_ex", "nst_gatys_buffer_bytes", "nst_vgg_features", "nst_gatys_targets",
                      "nst_gatys_grad", "nst_adam_step", "nst_create", "nst_create_ex", "nst_op_describe", "nst_forward_capture", "nst_output_hw", "nst_workspace_bytes", "nst_forward", "nst_decode_resize_u8",

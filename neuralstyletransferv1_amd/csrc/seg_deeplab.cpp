@@ -18,6 +18,17 @@
 //          the low-level 1x1 (256 -> 48, + 16 zero channels) into 256..319, two 3x3 + BN + ReLU,
 //          the 1x1 classifier with bias to fp32 logits
 //   head   bilinear (align_corners=True) to h x w fused with the argmax over classes.
+//
+// A second program (nst_seg_create_ex, NST_SEG_DRN_D54) runs the same network on the DRN-D-54 backbone
+// (modeling/backbone/drn.py:102-234, :386-387; deeplab.py:13-14 forces output stride 8 for it):
+//   head   layer0 7x7 3->16, layer1 3x3 16->16, layer2 3x3/2 16->32 at full resolution as direct convolutions
+//          (seg_drn_head.hip; normalisation fused into layer0); layer2's 32 channels are stored with the GEMM
+//          stage width as channel stride (zero padding channels), as the decoder's 304 -> 320 concat is
+//   layer3..layer6: the same Bottleneck launches — layer3 (3 blocks, stride 2: its output at 1/4 = the low-level
+//          features), layer4 (4, stride 2, -> 1/8), layer5 (6, dilation 2), layer6 (3, dilation 4); block 0 of
+//          layer5 / layer6 has a stride-1 downsample and the full dilation (new_level=False)
+//   layer7 3x3 dilation 2 2048 -> 512, layer8 3x3 512 -> 512, each + BN + ReLU
+//   ASPP on 512 channels at 1/8 with dilations 1, 12, 24, 36 (aspp.py:45-46), then the decoder and head above.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -81,6 +92,22 @@ const float* find_param(const ParamMap& pm, const std::string& name, int64_t num
   return it->second->data;
 }
 
+// eval BatchNorm2d (state_dict prefix bn) as per-channel scale / shift
+int fold_bn(const ParamMap& pm, const std::string& bn, int cout, float* sc, float* sh) {
+  int rc = NST_OK;
+  const float* g = find_param(pm, bn + ".weight", cout, &rc);
+  const float* b = g ? find_param(pm, bn + ".bias", cout, &rc) : nullptr;
+  const float* m = b ? find_param(pm, bn + ".running_mean", cout, &rc) : nullptr;
+  const float* v = m ? find_param(pm, bn + ".running_var", cout, &rc) : nullptr;
+  if (!v) return rc;
+  for (int c = 0; c < cout; ++c) {  // torch's batch_norm inference terms (float)
+    const float inv = 1.0f / std::sqrt(v[c] + 1e-5f);
+    sc[c] = inv * g[c];
+    sh[c] = b[c] - m[c] * sc[c];
+  }
+  return NST_OK;
+}
+
 // Pack W[cout][cin][k][k] (fp32) into [coutp/64][stage = tap*nck + cc][64 rows][stage channels] in the
 // compute dtype; eval BatchNorm (bn prefix) or a conv bias (bias name) into per-channel scale/shift.
 int build_conv(SegConv& L, const ParamMap& pm, const std::string& wname, const std::string& bn,
@@ -109,16 +136,7 @@ int build_conv(SegConv& L, const ParamMap& pm, const std::string& wname, const s
       }
   std::vector<float> sc(L.coutp, 0.f), sh(L.coutp, 0.f);
   if (!bn.empty()) {
-    const float* g = find_param(pm, bn + ".weight", L.cout, &rc);
-    const float* b = g ? find_param(pm, bn + ".bias", L.cout, &rc) : nullptr;
-    const float* m = b ? find_param(pm, bn + ".running_mean", L.cout, &rc) : nullptr;
-    const float* v = m ? find_param(pm, bn + ".running_var", L.cout, &rc) : nullptr;
-    if (!v) return rc;
-    for (int c = 0; c < L.cout; ++c) {  // torch's batch_norm inference terms (float)
-      const float inv = 1.0f / std::sqrt(v[c] + 1e-5f);
-      sc[c] = inv * g[c];
-      sh[c] = b[c] - m[c] * sc[c];
-    }
+    if ((rc = fold_bn(pm, bn, L.cout, sc.data(), sh.data())) != NST_OK) return rc;
   } else {
     const float* b = bias.empty() ? nullptr : find_param(pm, bias, L.cout, &rc);
     if (!bias.empty() && !b) return rc;
@@ -140,6 +158,35 @@ void free_conv(SegConv& L) {
   L.scale = L.shift = nullptr;
 }
 
+// One layer of the DRN head (seg_drn_head.hip): fp32 weights [tap][cin][cout] + the folded BatchNorm
+struct HeadConv {
+  float* w = nullptr;
+  float* scale = nullptr;
+  float* shift = nullptr;
+};
+
+int build_head_conv(HeadConv& L, const ParamMap& pm, const std::string& pre, int cin, int cout, int k) {
+  int rc = NST_OK;
+  const int kk = k * k;
+  const float* W = find_param(pm, pre + ".0.weight", (int64_t)cout * cin * kk, &rc);
+  if (!W) return rc;
+  std::vector<float> wt((size_t)kk * cin * cout), sc(cout), sh(cout);
+  for (int co = 0; co < cout; ++co)
+    for (int ci = 0; ci < cin; ++ci)
+      for (int t = 0; t < kk; ++t) wt[((size_t)t * cin + ci) * cout + co] = W[((size_t)co * cin + ci) * kk + t];
+  if ((rc = fold_bn(pm, pre + ".1", cout, sc.data(), sh.data())) != NST_OK) return rc;
+  if ((rc = upload_bytes(wt.data(), wt.size() * 4, (void**)&L.w)) != NST_OK) return rc;
+  if ((rc = upload_bytes(sc.data(), sc.size() * 4, (void**)&L.scale)) != NST_OK) return rc;
+  return upload_bytes(sh.data(), sh.size() * 4, (void**)&L.shift);
+}
+
+void free_head_conv(HeadConv& L) {
+  if (L.w) (void)hipFree(L.w);
+  if (L.scale) (void)hipFree(L.scale);
+  if (L.shift) (void)hipFree(L.shift);
+  L.w = L.scale = L.shift = nullptr;
+}
+
 int out_extent(int in, int k, int s, int d, int p) { return (in + 2 * p - d * (k - 1) - 1) / s + 1; }
 
 }  // namespace
@@ -151,10 +198,18 @@ struct nst_seg {
   int gemm_dt = NST_DT_BF16;
   int cache_n = 0, cache_h = 0, cache_w = 0;  // geometry of the cached workspace plan
   size_t cache_partial = 0;
+  int backbone = NST_SEG_RESNET101;
   SegConv stem;
-  std::vector<Bottleneck> blocks;  // layer1 (3), layer2 (4), layer3 (23), layer4 (3: multi-grid 1, 2, 4)
+  // resnet: layer1 (3), layer2 (4), layer3 (23), layer4 (3: multi-grid 1, 2, 4); drn: layer3 (3), layer4 (4),
+  // layer5 (6), layer6 (3).  layer_last[0]: the block whose output is the decoder's low-level feature map
+  std::vector<Bottleneck> blocks;
   int layer_last[4] = {0, 0, 0, 0};
+  int feat_c = 2048;  // channels the ASPP reads (drn: 512, layer8's)
   SegConv aspp[4], gap, proj, low, dec1, dec2, cls;
+  // drn only
+  HeadConv head[3];   // layer0..layer2
+  int head_cs = 0;    // channel stride of layer2's 32-channel output (the GEMM stage width)
+  SegConv l7, l8;
 };
 
 namespace {
@@ -162,6 +217,7 @@ namespace {
 struct SegPlan {
   int n = 0, h = 0, w = 0;
   int h2, w2, h4, w4, h8, w8, h16, w16;
+  size_t a0 = 0, a1 = 0, a2 = 0;  // drn: the head's three activations
   size_t col, stem, pool, x0, x1, t1, t2, r, lowf, cat5, gapv, gapo, aspo, dcat, d1, d2, logits, partial, end;
 };
 
@@ -173,7 +229,54 @@ struct SegRun {
   size_t partial_bytes = 0;
 };
 
+// drn: every strided step has extent (v - 1) / 2 + 1; block tensors up to 2048 channels at 1/8 (and layer3's first
+// 1x1 at 1/2), the ASPP concat of 1280 channels at 1/8, a pooled vector of 512
+SegPlan seg_plan_drn(const nst_seg* s, int n, int h, int w) {
+  SegPlan P;
+  P.n = n; P.h = h; P.w = w;
+  P.h2 = out_extent(h, 3, 2, 1, 1); P.w2 = out_extent(w, 3, 2, 1, 1);
+  P.h4 = out_extent(P.h2, 3, 2, 1, 1); P.w4 = out_extent(P.w2, 3, 2, 1, 1);
+  P.h8 = out_extent(P.h4, 3, 2, 1, 1); P.w8 = out_extent(P.w4, 3, 2, 1, 1);
+  P.h16 = P.h8; P.w16 = P.w8;  // unused: the features stay at 1/8
+  const size_t e = s->dtype == NST_DT_F32 ? 4 : 2;
+  const size_t p1 = (size_t)n * h * w, p2 = (size_t)n * P.h2 * P.w2, p4 = (size_t)n * P.h4 * P.w4;
+  const size_t p8 = (size_t)n * P.h8 * P.w8;
+  // walk the bottlenecks: outputs / downsample branches (big), the two planes-wide intermediates (mid)
+  size_t big = 0, mid = 0;
+  int hh = P.h2, ww = P.w2;
+  for (const Bottleneck& B : s->blocks) {
+    const int ho = out_extent(hh, 3, B.c2.stride, B.c2.dil, B.c2.pad), wo = out_extent(ww, 3, B.c2.stride, B.c2.dil, B.c2.pad);
+    mid = std::max(mid, (size_t)n * hh * ww * B.c1.cout * e);
+    big = std::max(big, (size_t)n * ho * wo * B.c3.cout * e);
+    hh = ho; ww = wo;
+  }
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t r = o; o += al256(bytes); return r; };
+  P.col = P.stem = P.pool = 0;
+  P.a0 = take(p1 * 16 * e);
+  P.a1 = take(p1 * 16 * e);
+  P.a2 = take(p2 * s->head_cs * e);
+  P.x0 = take(big);
+  P.x1 = take(big);
+  P.t1 = take(mid);
+  P.t2 = take(mid);
+  P.r = take(big);
+  P.lowf = take(p4 * 256 * e);
+  P.cat5 = take(p8 * 1280 * e);
+  P.gapv = take((size_t)n * s->feat_c * e);
+  P.gapo = take((size_t)n * 256 * e);
+  P.aspo = take(p8 * 256 * e);
+  P.dcat = take(p4 * 320 * e);
+  P.d1 = take(p4 * 256 * e);
+  P.d2 = take(p4 * 256 * e);
+  P.logits = take(p4 * s->ncs * 4);
+  P.partial = o;
+  P.end = o;
+  return P;
+}
+
 SegPlan seg_plan(const nst_seg* s, int n, int h, int w) {
+  if (s->backbone == NST_SEG_DRN_D54) return seg_plan_drn(s, n, h, w);
   SegPlan P;
   P.n = n; P.h = h; P.w = w;
   P.h2 = out_extent(h, 7, 2, 1, 3); P.w2 = out_extent(w, 7, 2, 1, 3);
@@ -248,14 +351,30 @@ int seg_forward_impl(nst_seg* s, const SegPlan& P, SegRun& R, const void* x, int
                      uint8_t* pred, char* ws, hipStream_t st) {
   const int n = P.n;
   const size_t e = s->dtype == NST_DT_F32 ? 4 : 2;
-  // stem
-  if (!R.dry) SEG_CHECK(launch_seg_stem_im2col(s->dtype, x, x_u8, n, P.h, P.w, P.h2, P.w2, s->stem.cinp, ws + P.col, st));
-  SEG_CHECK(run(s, R, s->stem, ws + P.col, n, P.h2, P.w2, s->stem.cinp, ws + P.stem, P.h2, P.w2, 64, 0, nullptr, 0, 1, 0,
-                64, st));
-  if (!R.dry) SEG_CHECK(launch_seg_maxpool(s->dtype, ws + P.stem, n, P.h2, P.w2, 64, ws + P.pool, P.h4, P.w4, st));
+  const bool drn = s->backbone == NST_SEG_DRN_D54;
+  const char* cur;
+  int ch, hh, ww;
+  if (drn) {
+    // head: three direct convolutions at full resolution; layer2 leaves 32 (+ zero padding) channels at 1/2
+    if (!R.dry) {
+      const HeadConv* H = s->head;
+      SEG_CHECK(launch_seg_drn_head(0, s->dtype, x, x_u8, n, P.h, P.w, H[0].w, H[0].scale, H[0].shift, ws + P.a0, 16, st));
+      SEG_CHECK(launch_seg_drn_head(1, s->dtype, ws + P.a0, 0, n, P.h, P.w, H[1].w, H[1].scale, H[1].shift, ws + P.a1, 16, st));
+      SEG_CHECK(launch_seg_drn_head(2, s->dtype, ws + P.a1, 0, n, P.h, P.w, H[2].w, H[2].scale, H[2].shift, ws + P.a2,
+                                    s->head_cs, st));
+    }
+    cur = ws + P.a2;
+    ch = s->head_cs; hh = P.h2; ww = P.w2;
+  } else {
+    // stem
+    if (!R.dry) SEG_CHECK(launch_seg_stem_im2col(s->dtype, x, x_u8, n, P.h, P.w, P.h2, P.w2, s->stem.cinp, ws + P.col, st));
+    SEG_CHECK(run(s, R, s->stem, ws + P.col, n, P.h2, P.w2, s->stem.cinp, ws + P.stem, P.h2, P.w2, 64, 0, nullptr, 0, 1, 0,
+                  64, st));
+    if (!R.dry) SEG_CHECK(launch_seg_maxpool(s->dtype, ws + P.stem, n, P.h2, P.w2, 64, ws + P.pool, P.h4, P.w4, st));
+    cur = ws + P.pool;
+    ch = 64; hh = P.h4; ww = P.w4;
+  }
   // residual layers
-  const char* cur = ws + P.pool;
-  int ch = 64, hh = P.h4, ww = P.w4;
   char* xb[2] = {ws + P.x0, ws + P.x1};
   int xi = 0;
   for (size_t b = 0; b < s->blocks.size(); ++b) {
@@ -275,12 +394,19 @@ int seg_forward_impl(nst_seg* s, const SegPlan& P, SegRun& R, const void* x, int
     cur = dst;
     ch = outc; hh = ho; ww = wo;
   }
-  // ASPP (input: layer4 output, 2048 channels at /16)
-  const int h16 = hh, w16 = ww;
+  if (drn) {
+    // layer7, layer8: plain conv + BN + ReLU at 1/8 (t1 / t2 hold 512 channels at 1/8: layer6's planes)
+    SEG_CHECK(run(s, R, s->l7, cur, n, hh, ww, ch, ws + P.t1, hh, ww, 512, 0, nullptr, 0, 1, 0, 512, st));
+    SEG_CHECK(run(s, R, s->l8, ws + P.t1, n, hh, ww, 512, ws + P.t2, hh, ww, 512, 0, nullptr, 0, 1, 0, 512, st));
+    cur = ws + P.t2;
+    ch = 512;
+  }
+  // ASPP (input: resnet layer4's output, 2048 channels at /16; drn layer8's, 512 channels at /8)
+  const int h16 = hh, w16 = ww, fc = s->feat_c;
   for (int i = 0; i < 4; ++i)
-    SEG_CHECK(run(s, R, s->aspp[i], cur, n, h16, w16, 2048, ws + P.cat5, h16, w16, 1280, 256 * i, nullptr, 0, 1, 0, 256, st));
-  if (!R.dry) SEG_CHECK(launch_seg_avgpool(s->dtype, cur, n, h16 * w16, 2048, 2048, ws + P.gapv, st));
-  SEG_CHECK(run(s, R, s->gap, ws + P.gapv, n, 1, 1, 2048, ws + P.gapo, 1, 1, 256, 0, nullptr, 0, 1, 0, 256, st));
+    SEG_CHECK(run(s, R, s->aspp[i], cur, n, h16, w16, fc, ws + P.cat5, h16, w16, 1280, 256 * i, nullptr, 0, 1, 0, 256, st));
+  if (!R.dry) SEG_CHECK(launch_seg_avgpool(s->dtype, cur, n, h16 * w16, fc, fc, ws + P.gapv, st));
+  SEG_CHECK(run(s, R, s->gap, ws + P.gapv, n, 1, 1, fc, ws + P.gapo, 1, 1, 256, 0, nullptr, 0, 1, 0, 256, st));
   if (!R.dry) SEG_CHECK(launch_seg_resize_ac(s->dtype, ws + P.gapo, n, 1, 1, 256, 256, ws + P.cat5, h16, w16, 1280, 1024, st));
   SEG_CHECK(run(s, R, s->proj, ws + P.cat5, n, h16, w16, 1280, ws + P.aspo, h16, w16, 256, 0, nullptr, 0, 1, 0, 256, st));
   // decoder
@@ -406,9 +532,15 @@ extern "C" {
 
 int nst_seg_create(const nst_param* params, int n_params, int num_classes, int compute_dtype, int device,
                    nst_seg** out) {
+  return nst_seg_create_ex(params, n_params, num_classes, compute_dtype, device, NST_SEG_RESNET101, out);
+}
+
+int nst_seg_create_ex(const nst_param* params, int n_params, int num_classes, int compute_dtype, int device,
+                      int backbone, nst_seg** out) {
   if (!params || n_params <= 0 || !out || num_classes < 2 || num_classes > 256 ||
       (compute_dtype != NST_DT_F32 && compute_dtype != NST_DT_BF16 && compute_dtype != NST_DT_F16 &&
-       compute_dtype != NST_DT_F32S)) {
+       compute_dtype != NST_DT_F32S) ||
+      (backbone != NST_SEG_RESNET101 && backbone != NST_SEG_DRN_D54)) {
     set_error("nst_seg_create: invalid arguments");
     return NST_E_INVALID;
   }
@@ -426,6 +558,7 @@ int nst_seg_create(const nst_param* params, int n_params, int num_classes, int c
   s->dtype = compute_dtype;
   s->nc = num_classes;
   s->ncs = (num_classes + 3) / 4 * 4;
+  s->backbone = backbone;
   const int ck = gemm_stage_channels(compute_dtype);
   int rc = NST_OK;
   auto conv = [&](SegConv& L, int cin, int cout, int k, int stride, int dil, int pad, const std::string& wname,
@@ -434,8 +567,9 @@ int nst_seg_create(const nst_param* params, int n_params, int num_classes, int c
     L.cin = cin; L.cout = cout; L.k = k; L.stride = stride; L.dil = dil; L.pad = pad;
     rc = build_conv(L, pm, wname, bn, bias, compute_dtype, cinp);
   };
+  const bool drn = backbone == NST_SEG_DRN_D54;
   // stem: the 7x7x3 taps as one K = 147 row (the im2col buffer), padded to the stage width
-  {
+  if (!drn) {
     auto it = pm.find("backbone.conv1.weight");
     if (it == pm.end() || it->second->numel != 64 * 3 * 49) {
       set_error("missing or mis-shaped DeepLab tensor backbone.conv1.weight");
@@ -458,7 +592,7 @@ int nst_seg_create(const nst_param* params, int n_params, int num_classes, int c
   // (:70, :94-111: stride 1, dilations 2*{1,2,4})
   const int nblocks[3] = {3, 4, 23}, planes_of[4] = {64, 128, 256, 512}, stride_of[4] = {1, 2, 2, 1};
   int inplanes = 64;
-  for (int l = 0; l < 4 && rc == NST_OK; ++l) {
+  for (int l = 0; l < 4 && rc == NST_OK && !drn; ++l) {
     const int nb = l < 3 ? nblocks[l] : 3, planes = planes_of[l];
     for (int i = 0; i < nb && rc == NST_OK; ++i) {
       Bottleneck B;
@@ -477,13 +611,45 @@ int nst_seg_create(const nst_param* params, int n_params, int num_classes, int c
     }
     s->layer_last[l] = (int)s->blocks.size() - 1;
   }
-  // ASPP (aspp.py:43-60, output stride 16: dilations 1, 6, 12, 18)
-  const int adil[4] = {1, 6, 12, 18};
+  if (drn) {
+    // head (drn.py:124-134), then layer3..layer6 (drn.py:136-142, :172-194): strides 2, 2, 1, 1, dilations 1, 1, 2, 4
+    // on every conv2 (new_level=False: block 0 too), a downsample on each layer's block 0; layer7 / layer8 (:151-155)
+    s->head_cs = (32 + ck - 1) / ck * ck;
+    const int hk[3] = {7, 3, 3}, hcin[3] = {3, 16, 16}, hcout[3] = {16, 16, 32};
+    for (int l = 0; l < 3 && rc == NST_OK; ++l)
+      rc = build_head_conv(s->head[l], pm, "backbone.layer" + std::to_string(l), hcin[l], hcout[l], hk[l]);
+    const int dnb[4] = {3, 4, 6, 3}, dplanes[4] = {64, 128, 256, 512}, dstride[4] = {2, 2, 1, 1}, ddil[4] = {1, 1, 2, 4};
+    inplanes = 32;
+    for (int l = 0; l < 4 && rc == NST_OK; ++l) {
+      for (int i = 0; i < dnb[l] && rc == NST_OK; ++i) {
+        Bottleneck B;
+        const std::string pre = "backbone.layer" + std::to_string(l + 3) + "." + std::to_string(i);
+        const int stride = i == 0 ? dstride[l] : 1, planes = dplanes[l];
+        conv(B.c1, inplanes, planes, 1, 1, 1, 0, pre + ".conv1.weight", pre + ".bn1");
+        conv(B.c2, planes, planes, 3, stride, ddil[l], ddil[l], pre + ".conv2.weight", pre + ".bn2");
+        conv(B.c3, planes, planes * 4, 1, 1, 1, 0, pre + ".conv3.weight", pre + ".bn3");
+        if (i == 0) {
+          B.has_ds = true;
+          conv(B.ds, inplanes, planes * 4, 1, stride, 1, 0, pre + ".downsample.0.weight", pre + ".downsample.1");
+        }
+        inplanes = planes * 4;
+        s->blocks.push_back(B);
+      }
+      s->layer_last[l] = (int)s->blocks.size() - 1;
+    }
+    conv(s->l7, 2048, 512, 3, 1, 2, 2, "backbone.layer7.0.weight", "backbone.layer7.1");
+    conv(s->l8, 512, 512, 3, 1, 1, 1, "backbone.layer8.0.weight", "backbone.layer8.1");
+    s->feat_c = 512;
+  }
+  // ASPP (aspp.py:43-60; resnet at output stride 16: dilations 1, 6, 12, 18; drn at 8: 1, 12, 24, 36)
+  const int adil16[4] = {1, 6, 12, 18}, adil8[4] = {1, 12, 24, 36};
+  const int* adil = drn ? adil8 : adil16;
+  const int fc = s->feat_c;
   for (int i = 0; i < 4; ++i) {
     const std::string pre = "aspp.aspp" + std::to_string(i + 1);
-    conv(s->aspp[i], 2048, 256, i == 0 ? 1 : 3, 1, adil[i], i == 0 ? 0 : adil[i], pre + ".atrous_conv.weight", pre + ".bn");
+    conv(s->aspp[i], fc, 256, i == 0 ? 1 : 3, 1, adil[i], i == 0 ? 0 : adil[i], pre + ".atrous_conv.weight", pre + ".bn");
   }
-  conv(s->gap, 2048, 256, 1, 1, 1, 0, "aspp.global_avg_pool.1.weight", "aspp.global_avg_pool.2");
+  conv(s->gap, fc, 256, 1, 1, 1, 0, "aspp.global_avg_pool.1.weight", "aspp.global_avg_pool.2");
   conv(s->proj, 1280, 256, 1, 1, 1, 0, "aspp.conv1.weight", "aspp.bn1");
   // decoder (decoder.py:19-30); the 304-channel concat is stored as 320 (16 zero channels)
   conv(s->low, 256, 48, 1, 1, 1, 0, "decoder.conv1.weight", "decoder.bn1");
@@ -507,6 +673,8 @@ void nst_seg_destroy(nst_seg* s) {
   }
   for (auto& L : s->aspp) free_conv(L);
   free_conv(s->gap); free_conv(s->proj); free_conv(s->low); free_conv(s->dec1); free_conv(s->dec2); free_conv(s->cls);
+  for (auto& H : s->head) free_head_conv(H);
+  free_conv(s->l7); free_conv(s->l8);
   delete s;
 }
 

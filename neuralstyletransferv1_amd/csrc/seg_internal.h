@@ -57,6 +57,15 @@ inline int gemm_stage_channels(int dtype) { return (dtype == NST_DT_F32 || dtype
 // of output pixel (n,oy,ox) -> col [npix][kp] (zero padding, zero columns k >= 147).
 hipError_t launch_seg_stem_im2col(int dtype, const void* x, int x_u8, int n, int h, int w, int ho, int wo, int kp,
                                   void* col, hipStream_t st);
+// ---- seg_drn_head.hip ----
+// One layer of the DRN-D head (drn.py:124-134: layer0 7x7 3->16, layer1 3x3 16->16, layer2 3x3/2 16->32, each +
+// BatchNorm + ReLU) at full input resolution as a direct convolution: no im2col buffer, fp32 accumulation, output
+// NHWC in the activation dtype with channel stride out_cs (channels past the layer's count written as zeros).
+// layer 0 reads the module input f32 NCHW [n][3][h][w] or (x_u8) frames u8 NHWC with preprocess_pil fused, zero
+// padding after the normalisation; layers 1 and 2 read dense NHWC [n][h][w][16] in the activation dtype.
+// wt: fp32 [ky*K+kx][cin][cout]; scale / shift: the folded BatchNorm, [cout].  h, w: the layer's INPUT extent.
+hipError_t launch_seg_drn_head(int layer, int dtype, const void* in, int x_u8, int n, int h, int w, const float* wt,
+                               const float* scale, const float* shift, void* out, int out_cs, hipStream_t st);
 // MaxPool2d(3, 2, 1) NHWC (channel stride c)
 hipError_t launch_seg_maxpool(int dtype, const void* in, int n, int h, int w, int c, void* out, int ho, int wo,
                               hipStream_t st);

@@ -1,11 +1,12 @@
-"""DeepLab v3+ (ResNet-101, output stride 16) mask network — drop-in for the reference's
-modeling/deeplab.py as sky_swap.py:143-177 `load_deeplab` builds it (backbone 'resnet', BatchNorm2d,
-eval mode), plus the GPU mask path of sky_swap.py:185-219 `infer_mask` and :271-366
+"""DeepLab v3+ mask network (ResNet-101 at output stride 16, or DRN-D-54 at output stride 8) — drop-in for the
+reference's modeling/deeplab.py as sky_swap.py:143-177 `load_deeplab` builds it (backbone 'resnet' or 'drn',
+BatchNorm2d, eval mode), plus the GPU mask path of sky_swap.py:185-219 `infer_mask` and :271-366
 `batch_masks_from_frames` (BASELINE.json configs[4]).
 
 `DeepLab` keeps the reference module's submodule names and parameter shapes
 (backbone.layer3.22.conv2.weight, aspp.global_avg_pool.1.weight, decoder.last_conv.8.bias, ...), so a
-`deeplab-resnet.pth.tar` state_dict loads unchanged; its parameters are containers only and `forward`
+`deeplab-resnet.pth.tar` state_dict loads unchanged (`DeepLabDRN`: backbone.layer0.0.weight,
+backbone.layer6.2.conv2.weight, ... for a `deeplab-drn.pth.tar`); its parameters are containers only and `forward`
 runs the network as libnst_hip kernels (csrc/seg_deeplab.cpp, csrc/conv_gemm.hip).  There is no CPU
 path.  `MaskEngine` is the frame-batch API the stylization pipeline uses: frames in HBM ->
 LANCZOS working-size downscale -> DeepLab -> argmax -> class selection -> close / expand / contract /
@@ -25,6 +26,8 @@ from ._lib import NstError, NstParam, check, lib
 
 _DTYPES = {"fp32": _lib.NST_DT_F32, "float32": _lib.NST_DT_F32, "bf16": _lib.NST_DT_BF16, "bfloat16": _lib.NST_DT_BF16,
            "fp16": _lib.NST_DT_F16, "float16": _lib.NST_DT_F16, "fp32s": _lib.NST_DT_F32S}
+
+_BACKBONES = {"resnet": _lib.NST_SEG_RESNET101, "drn": _lib.NST_SEG_DRN_D54}
 
 # resnet.py:153 ResNet101 blocks per layer; :50-56 output stride 16 strides / dilations; :50 multi-grid
 RESNET101_LAYERS = (3, 4, 23)
@@ -73,6 +76,45 @@ class ResNet(nn.Module):
             setattr(self, f"layer{li + 1}", nn.Sequential(*blocks))
 
 
+# drn.py:386-387 drn_d_54 = DRN(Bottleneck, [1, 1, 3, 4, 6, 3, 1, 1], arch='D'), channels :105
+DRN_D54_LAYERS = (1, 1, 3, 4, 6, 3, 1, 1)
+DRN_CHANNELS = (16, 32, 64, 128, 256, 512, 512, 512)
+
+
+def _conv_layers(inplanes: int, channels: int, convs: int, stride: int = 1, dilation: int = 1) -> nn.Sequential:
+    """drn.py:196-206 _make_conv_layers."""
+    mods = []
+    for i in range(convs):
+        mods += [nn.Conv2d(inplanes, channels, 3, stride=stride if i == 0 else 1, padding=dilation, bias=False,
+                           dilation=dilation), _bn(channels), nn.ReLU(inplace=True)]
+        inplanes = channels
+    return nn.Sequential(*mods)
+
+
+class DRN(nn.Module):
+    """drn.py:102-157 for arch 'D' with Bottleneck blocks (DRN-D-54): a 7x7 + 3x3 + 3x3/2 head at full input
+    resolution, layer3 / layer4 with stride 2, layer5 / layer6 with dilation 2 / 4 at 1/8 (new_level=False: block 0
+    uses the full dilation too, and a stride-1 downsample for the channel change), two plain dilated conv layers."""
+
+    def __init__(self):
+        super().__init__()
+        ch, nb = DRN_CHANNELS, DRN_D54_LAYERS
+        self.layer0 = nn.Sequential(nn.Conv2d(3, ch[0], 7, stride=1, padding=3, bias=False), _bn(ch[0]),
+                                    nn.ReLU(inplace=True))
+        self.layer1 = _conv_layers(ch[0], ch[0], nb[0], stride=1)
+        self.layer2 = _conv_layers(ch[0], ch[1], nb[1], stride=2)
+        inplanes = ch[1]
+        for li, (stride, dil) in zip((3, 4, 5, 6), ((2, 1), (2, 1), (1, 2), (1, 4))):
+            planes = ch[li - 1]
+            blocks = []
+            for i in range(nb[li - 1]):
+                blocks.append(Bottleneck(inplanes, planes, stride if i == 0 else 1, dil, downsample=(i == 0)))
+                inplanes = planes * 4
+            setattr(self, f"layer{li}", nn.Sequential(*blocks))
+        self.layer7 = _conv_layers(inplanes, ch[6], nb[6], dilation=2)
+        self.layer8 = _conv_layers(ch[6], ch[7], nb[7], dilation=1)
+
+
 class _ASPPModule(nn.Module):
     """aspp.py:7-21."""
 
@@ -85,15 +127,16 @@ class _ASPPModule(nn.Module):
 
 
 class ASPP(nn.Module):
-    """aspp.py:34-78 for the resnet backbone at output stride 16 (dilations 1, 6, 12, 18)."""
+    """aspp.py:34-78: the defaults are the resnet backbone at output stride 16 (2048 channels in, dilations 1, 6, 12,
+    18); drn: 512 channels in, output stride 8 (dilations 1, 12, 24, 36)."""
 
-    def __init__(self):
+    def __init__(self, inplanes: int = 2048, dilations: Sequence[int] = (1, 6, 12, 18)):
         super().__init__()
-        for i, d in enumerate((1, 6, 12, 18)):
-            k = 1 if d == 1 else 3
-            setattr(self, f"aspp{i + 1}", _ASPPModule(2048, 256, k, 0 if k == 1 else d, d))
-        self.global_avg_pool = nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)), nn.Conv2d(2048, 256, 1, stride=1, bias=False),
-                                             _bn(256), nn.ReLU())
+        for i, d in enumerate(dilations):
+            k = 1 if i == 0 else 3
+            setattr(self, f"aspp{i + 1}", _ASPPModule(inplanes, 256, k, 0 if k == 1 else d, d))
+        self.global_avg_pool = nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)),
+                                             nn.Conv2d(inplanes, 256, 1, stride=1, bias=False), _bn(256), nn.ReLU())
         self.conv1 = nn.Conv2d(1280, 256, 1, bias=False)
         self.bn1 = _bn(256)
         self.relu = nn.ReLU()
@@ -101,11 +144,11 @@ class ASPP(nn.Module):
 
 
 class Decoder(nn.Module):
-    """decoder.py:7-43 (resnet: 256 low-level channels)."""
+    """decoder.py:7-43 (resnet and drn: 256 low-level channels)."""
 
-    def __init__(self, num_classes: int):
+    def __init__(self, num_classes: int, low_level_inplanes: int = 256):
         super().__init__()
-        self.conv1 = nn.Conv2d(256, 48, 1, bias=False)
+        self.conv1 = nn.Conv2d(low_level_inplanes, 48, 1, bias=False)
         self.bn1 = _bn(48)
         self.relu = nn.ReLU()
         self.last_conv = nn.Sequential(
@@ -117,7 +160,11 @@ class Decoder(nn.Module):
 class SegEngine:
     """One packed DeepLab checkpoint on one device (owns an nst_seg handle and a workspace)."""
 
-    def __init__(self, state: Dict[str, torch.Tensor], num_classes: int, dtype: str, device: torch.device):
+    def __init__(self, state: Dict[str, torch.Tensor], num_classes: int, dtype: str, device: torch.device,
+                 backbone: str = "resnet"):
+        if backbone not in _BACKBONES:
+            raise NstError(f"backbone must be resnet or drn, got {backbone!r}")
+        self.backbone = backbone
         if device.type != "cuda":
             raise NstError("libnst_hip runs on MI355X (cuda) devices only; there is no CPU path")
         if dtype not in _DTYPES:
@@ -138,8 +185,8 @@ class SegEngine:
             arr[i].numel = host[k].numel()
         h = ctypes.c_void_p()
         dev_index = device.index if device.index is not None else torch.cuda.current_device()
-        check(lib().nst_seg_create(arr, len(names), self.num_classes, self.dtype, dev_index, ctypes.byref(h)),
-              "nst_seg_create")
+        check(lib().nst_seg_create_ex(arr, len(names), self.num_classes, self.dtype, dev_index, _BACKBONES[backbone],
+                                      ctypes.byref(h)), "nst_seg_create_ex")
         self._h = h
         self._ws: Optional[torch.Tensor] = None
 
@@ -185,19 +232,14 @@ class SegEngine:
         return lg, pr
 
 
-class DeepLab(nn.Module):
-    """modeling/deeplab.py:9-33 with backbone='resnet', output_stride=16, sync_bn=False (sky_swap.py:160-166)."""
+class _DeepLabBase(nn.Module):
+    """What the two DeepLab modules share: the parameters are containers, forward() runs the packed network of
+    `backbone_kind` as libnst_hip kernels through a per-(device, dtype) SegEngine rebuilt when the parameters change."""
 
-    def __init__(self, backbone: str = "resnet", output_stride: int = 16, num_classes: int = 21, sync_bn: bool = True,
-                 freeze_bn: bool = False):
-        super().__init__()
-        if backbone != "resnet" or output_stride != 16:
-            raise NstError("libnst_hip builds DeepLab v3+ with backbone='resnet', output_stride=16 "
-                           "(what sky_swap.py load_deeplab uses)")
+    backbone_kind = "resnet"
+
+    def _init_engine_state(self, num_classes: int, freeze_bn: bool) -> None:
         self.num_classes = int(num_classes)
-        self.backbone = ResNet()
-        self.aspp = ASPP()
-        self.decoder = Decoder(num_classes)
         self.freeze_bn = freeze_bn
         self.compute_dtype = "fp32"
         self._engines: Dict[Tuple[int, str], Tuple[tuple, SegEngine]] = {}
@@ -219,7 +261,7 @@ class DeepLab(nn.Module):
         hit = self._engines.get(key)
         if hit is not None and hit[0] == pk:
             return hit[1]
-        eng = SegEngine(self.state_dict(), self.num_classes, dtype, device)
+        eng = SegEngine(self.state_dict(), self.num_classes, dtype, device, self.backbone_kind)
         self._engines[key] = (pk, eng)
         return eng
 
@@ -230,6 +272,38 @@ class DeepLab(nn.Module):
     def _apply(self, fn, *args, **kwargs):
         self._engines = {}
         return super()._apply(fn, *args, **kwargs)
+
+
+class DeepLab(_DeepLabBase):
+    """modeling/deeplab.py:9-33 with backbone='resnet', output_stride=16, sync_bn=False (sky_swap.py:160-166)."""
+
+    def __init__(self, backbone: str = "resnet", output_stride: int = 16, num_classes: int = 21, sync_bn: bool = True,
+                 freeze_bn: bool = False):
+        super().__init__()
+        if backbone == "drn":
+            raise NstError("DeepLab builds backbone='resnet'; the DRN-D-54 network (backbone='drn', output stride 8) "
+                           "is DeepLabDRN, or load_deeplab(..., backbone='drn')")
+        if backbone != "resnet" or output_stride != 16:
+            raise NstError("libnst_hip builds DeepLab v3+ with backbone='resnet', output_stride=16 "
+                           "(what sky_swap.py load_deeplab uses)")
+        self.backbone = ResNet()
+        self.aspp = ASPP()
+        self.decoder = Decoder(num_classes)
+        self._init_engine_state(num_classes, freeze_bn)
+
+
+class DeepLabDRN(_DeepLabBase):
+    """modeling/deeplab.py:9-33 with backbone='drn': DRN-D-54, output stride forced to 8 (deeplab.py:13-14), ASPP on
+    512 channels with dilations 1, 12, 24, 36, the decoder on layer3's 256 low-level channels at 1/4."""
+
+    backbone_kind = "drn"
+
+    def __init__(self, num_classes: int = 21, sync_bn: bool = True, freeze_bn: bool = False):
+        super().__init__()
+        self.backbone = DRN()
+        self.aspp = ASPP(512, (1, 12, 24, 36))
+        self.decoder = Decoder(num_classes, 256)
+        self._init_engine_state(num_classes, freeze_bn)
 
 
 class Resampler:
@@ -312,7 +386,7 @@ class MaskEngine:
     target-id selection, close 5x5, expand / contract / feather (px or percent of the working height),
     INTER_LINEAR upscale back to the frame size."""
 
-    def __init__(self, model: DeepLab, device: torch.device, resolution: int = 256, dtype: Optional[str] = None):
+    def __init__(self, model: _DeepLabBase, device: torch.device, resolution: int = 256, dtype: Optional[str] = None):
         self.model = model
         self.device = torch.device(device)
         self.resolution = int(resolution or 0)
@@ -384,16 +458,27 @@ def detect_num_classes(state: Dict[str, torch.Tensor]) -> Optional[int]:
     return max(cand) if cand else None
 
 
-def load_deeplab(weights_path: str, num_classes: Optional[int] = None, device="cuda", dtype: str = "bf16"):
+def load_deeplab(weights_path: str, num_classes: Optional[int] = None, device="cuda", dtype: str = "bf16",
+                 backbone: str = "resnet"):
     """sky_swap.py:143-177: checkpoint (optionally {"state_dict": ...}, "module." prefixes stripped), class count
-    sniffed from the 1x1 convs, load_state_dict(strict=False).  Loaded with weights_only=True."""
+    sniffed from the 1x1 convs, load_state_dict(strict=False).  Loaded with weights_only=True.  backbone: "resnet"
+    (DeepLab) or "drn" (DeepLabDRN); a checkpoint whose keys belong to the other backbone gets one [warn] line."""
+    if backbone not in _BACKBONES:
+        raise NstError(f"backbone must be resnet or drn, got {backbone!r}")
     ckpt = torch.load(weights_path, map_location="cpu", weights_only=True)
     state = ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt
     state = {k.replace("module.", "", 1): v for k, v in state.items()}
     detected = detect_num_classes(state)
     nc = num_classes if num_classes is not None else (detected if detected is not None else 19)
-    print(f"[info] using num_classes={nc} (detected={detected}) backbone=resnet")
-    model = DeepLab(num_classes=nc, backbone="resnet", output_stride=16, sync_bn=False, freeze_bn=False)
+    print(f"[info] using num_classes={nc} (detected={detected}) backbone={backbone}")
+    other_key = {"resnet": "backbone.layer0.0.weight", "drn": "backbone.conv1.weight"}[backbone]
+    if other_key in state:
+        print(f"[warn] checkpoint has {other_key}: it looks like a "
+              f"{'drn' if backbone == 'resnet' else 'resnet'} checkpoint, not --backbone {backbone}")
+    if backbone == "drn":
+        model = DeepLabDRN(num_classes=nc, sync_bn=False, freeze_bn=False)
+    else:
+        model = DeepLab(num_classes=nc, backbone="resnet", output_stride=16, sync_bn=False, freeze_bn=False)
     missing, unexpected = model.load_state_dict(state, strict=False)
     if missing or unexpected:
         print(f"[warn] load_state: missing={len(missing)} unexpected={len(unexpected)}")
@@ -401,13 +486,19 @@ def load_deeplab(weights_path: str, num_classes: Optional[int] = None, device="c
     return model.eval().to(device), int(nc)
 
 
-def make_state_dict(num_classes: int = 19, seed: int = 0) -> Dict[str, torch.Tensor]:
+def make_state_dict(num_classes: int = 19, seed: int = 0, backbone: str = "resnet") -> Dict[str, torch.Tensor]:
     """Seeded synthetic DeepLab checkpoint with the reference's keys (the .pth.tar is not shipped:
-    .gitignore:12-13).  numpy PCG64; convs N(0, 2/fan_in); BatchNorm gamma U(0.5, 1), beta U(-0.1, 0.1),
+    .gitignore:12-13), for the resnet module or (backbone="drn") the DRN one: the same rules over that module's
+    keys in its state_dict order, with the same constants (the resnet output is byte-identical to what the
+    deeplab_s*.npz goldens pin).  numpy PCG64; convs N(0, 2/fan_in); BatchNorm gamma U(0.5, 1), beta U(-0.1, 0.1),
     running_mean U(-0.1, 0.1), running_var U(0.5, 1.5); each bottleneck's bn3 gamma U(0.1, 0.3) so the
-    residual stream stays O(1) over 33 blocks; classifier N(0, 1/fan_in) with zero-sum rows, bias U(-0.1, 0.1)."""
+    residual stream stays O(1) over 33 (drn: 16) blocks; classifier N(0, 1/fan_in) with zero-sum rows, bias
+    U(-0.1, 0.1)."""
     rng = np.random.Generator(np.random.PCG64(seed))
-    template = DeepLab(num_classes=num_classes).state_dict()
+    if backbone not in _BACKBONES:
+        raise NstError(f"backbone must be resnet or drn, got {backbone!r}")
+    module = DeepLabDRN(num_classes=num_classes) if backbone == "drn" else DeepLab(num_classes=num_classes)
+    template = module.state_dict()
     out: Dict[str, torch.Tensor] = {}
     for name, t in template.items():
         shape = tuple(t.shape)

@@ -8,6 +8,9 @@ CPU path).  Usage as in the reference, e.g.
 
     python -m neuralstyletransferv1_amd.sky_swap --batch_frames work/frames --weights deeplab-resnet.pth.tar \\
         --target_labels person --mask_feather 3
+
+`--backbone drn` takes the DRN-D-54 checkpoint (`--weights deeplab-drn.pth.tar`, sky_swap.py:372-373); everything
+after the model load is the same.
 """
 from __future__ import annotations
 
@@ -163,7 +166,9 @@ def main(argv=None) -> int:
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--image", required=False)
     ap.add_argument("--weights", required=True)
-    ap.add_argument("--backbone", choices=["resnet", "drn"], default="resnet")
+    ap.add_argument("--backbone", choices=["resnet", "drn"], default="resnet",
+                    help="DeepLab backbone of the checkpoint: resnet (ResNet-101, deeplab-resnet.pth.tar) or drn "
+                         "(DRN-D-54 at output stride 8, deeplab-drn.pth.tar)")
     ap.add_argument("--sky_id", type=int, default=deeplab.CITYSCAPES_SKY_ID_DEFAULT)
     ap.add_argument("--num_classes", type=int, default=None)
     ap.add_argument("--scan_sky", action="store_true")
@@ -201,15 +206,13 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if not args.batch_frames and not args.image:
         ap.error("either --image or --batch_frames must be provided")
-    if args.backbone != "resnet":
-        ap.error("libnst_hip builds the resnet backbone (the one sky_swap.py's configs use)")
     for path, label in ((args.image, "input image"), (args.weights, "weights checkpoint"), (args.plate, "sky plate")):
         if path and not os.path.exists(path):
             raise FileNotFoundError(f"[error] {label} not found: {path}")
     if args.device != "cuda":
         print(f"[note] --device {args.device}: the mask network runs on the MI355X (libnst_hip has no CPU path)")
     dev = torch.device("cuda", torch.cuda.current_device())
-    model, used_nc = deeplab.load_deeplab(args.weights, args.num_classes, dev, args.dtype)
+    model, used_nc = deeplab.load_deeplab(args.weights, args.num_classes, dev, args.dtype, backbone=args.backbone)
     if args.batch_frames:
         batch_masks(args, model, used_nc, dev)
         return 0

@@ -6,7 +6,14 @@ Step = one batch of 8 HBM-resident 1920x1080 uint8 frames through
   + Johnson stylization (bf16)                                                        [pipeline.py:1445-1519]
   + mask composite, keep mode (alpha = m / 255)                                        [pipeline.py:1984-2048]
 Prints one JSON line: frames/s of the whole step, ms of each stage, and the DeepLab forward's algorithmic
-TFLOP/s at the working size and at full 1080p (--resolution 0), which is where conv_gemm is MFMA-bound."""
+TFLOP/s at the working size and at full 1080p (--resolution 0), which is where conv_gemm is MFMA-bound.
+
+    python tools/seg_bench.py [--backbone {resnet,drn}]
+
+--backbone drn times the DRN-D-54 network (sky_swap.py --backbone drn) in the same step; its FLOP count is
+drn_gflop, and the JSON line also carries the head's (csrc/seg_drn_head.hip) algorithmic FLOPs and HBM bytes per
+1080p frame, to set against the head kernels' times in a kernel trace of this tool."""
+import argparse
 import json
 import os
 import sys
@@ -49,6 +56,40 @@ def deeplab_gflop(h, w, nc=19):
     return 2 * macs / 1e9
 
 
+def drn_gflop(h, w, nc=19):
+    """2 * MACs of every conv of the DRN-D-54 DeepLab v3+ (output stride 8) at input h x w; [1]: the head's share
+    (layer0..layer2 at full resolution)."""
+    def half(v):
+        return (v - 1) // 2 + 1
+    h2, w2 = half(h), half(w)
+    head = h * w * (16 * 147 + 16 * 144) + h2 * w2 * 32 * 144
+    macs = head
+    hh, ww, inpl = h2, w2, 32
+    h4 = w4 = 0
+    for li, (nb, planes, stride) in enumerate(((3, 64, 2), (4, 128, 2), (6, 256, 1), (3, 512, 1))):
+        for i in range(nb):
+            s = stride if i == 0 else 1
+            ho, wo = (half(hh), half(ww)) if s == 2 else (hh, ww)
+            macs += hh * ww * inpl * planes + ho * wo * planes * planes * 9 + ho * wo * planes * planes * 4
+            if i == 0:
+                macs += ho * wo * inpl * planes * 4
+            inpl = planes * 4
+            hh, ww = ho, wo
+        if li == 0:
+            h4, w4 = hh, ww
+    macs += hh * ww * (2048 * 512 * 9 + 512 * 512 * 9)                                  # layer7, layer8
+    macs += hh * ww * 512 * 256 * (1 + 9 * 3) + 512 * 256 + hh * ww * 1280 * 256        # ASPP
+    macs += h4 * w4 * (256 * 48 + 304 * 256 * 9 + 256 * 256 * 9 + 256 * nc)             # decoder
+    return 2 * macs / 1e9, 2 * head / 1e9
+
+
+def drn_head_bytes(h, w, esz, cs2):
+    """HBM bytes the three head kernels have to move per u8 frame: [read, write] per layer (activations of esz
+    bytes; layer2 writes cs2 channels)."""
+    h2, w2 = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    return [[h * w * 3, h * w * 16 * esz], [h * w * 16 * esz, h * w * 16 * esz], [h * w * 16 * esz, h2 * w2 * cs2 * esz]]
+
+
 def timed(fn, steps):
     for _ in range(2):
         fn()
@@ -66,9 +107,14 @@ MASK_DT = os.environ.get("SEG_MASK_DT", "fp32s")
 
 
 def main():
-    model = deeplab.DeepLab(num_classes=19)
-    model.load_state_dict(deeplab.make_state_dict(19, 0))
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--backbone", choices=["resnet", "drn"], default="resnet")
+    args = ap.parse_args()
+    drn = args.backbone == "drn"
+    model = deeplab.DeepLabDRN(num_classes=19) if drn else deeplab.DeepLab(num_classes=19)
+    model.load_state_dict(deeplab.make_state_dict(19, 0, backbone=args.backbone))
     model = model.eval().to(dev)
+    gflop = (lambda h, w: drn_gflop(h, w)[0]) if drn else deeplab_gflop
     net = TransformerNet()
     net.load_state_dict(synthetic.make_state_dict("johnson", seed=0))
     net = net.to(dev).eval()
@@ -77,7 +123,11 @@ def main():
     frames = torch.from_numpy(synthetic.make_frames(N, H, W, seed=77)).to(dev)
     ids = [10]  # Cityscapes "sky" (sky_swap.py:83)
     out = {"workload": "configs[4]: DeepLab v3+ mask (256-px working size) + Johnson stylization + mask composite, "
-                       "1920x1080 batch 8, bf16", "frames_per_step": N}
+                       "1920x1080 batch 8, bf16", "frames_per_step": N, "backbone": args.backbone}
+    if drn:
+        esz = 2 if MASK_DT in ("bf16", "fp16") else 4
+        out["drn_head_per_1080p_frame"] = {"gflop": round(drn_gflop(H, W)[1], 2), "dtype": MASK_DT,
+                                           "bytes_read_write_per_layer": drn_head_bytes(H, W, esz, 64 if esz == 2 else 32)}
     res = {}
     for dtype in os.environ.get("SEG_DTYPES", "bf16,fp16,fp32,fp32s").split(","):
         me = deeplab.MaskEngine(model, dev, resolution=256, dtype=dtype)
@@ -88,7 +138,7 @@ def main():
     seg = model.engine(dev, MASK_DT)
     fwd_ms = timed(lambda: seg.run(work, logits=False, pred=True), STEPS)
     lanczos_ms = timed(lambda: me._resampler("lanczos", H, W, hw[1], hw[0])(frames), STEPS)
-    g_work = deeplab_gflop(hw[1], hw[0]) * N
+    g_work = gflop(hw[1], hw[0]) * N
     out.update({"mask_dtype": MASK_DT, **{f"mask_ms_{d}": round(t, 3) for d, t in res.items()},
                 "lanczos_ms": round(lanczos_ms, 3), "deeplab_fwd_ms": round(fwd_ms, 3),
                 "deeplab_gflop_per_batch": round(g_work, 2),
@@ -96,7 +146,7 @@ def main():
     # full-resolution DeepLab (sky_swap --resolution 0): large GEMMs, two frames
     big = frames[:2].contiguous()
     full_ms = timed(lambda: seg.run(big, logits=False, pred=True), max(3, STEPS // 3))
-    g_full = deeplab_gflop(H, W) * 2
+    g_full = gflop(H, W) * 2
     out.update({"deeplab_fullres_ms_2frames": round(full_ms, 3), "deeplab_fullres_gflop_2frames": round(g_full, 1),
                 "deeplab_fullres_tflops": round(g_full / full_ms, 1)})
     # the whole configs[4] step
