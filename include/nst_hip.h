@@ -561,6 +561,48 @@ int nst_flow_fuse(const float* curr, const float* prev, const float* flow, int h
 int nst_motion_alpha(const float* flow, int h, int w, float motion_norm, double sigma, float max_alpha, float span,
                      float* alpha, float* scratch, void* stream);
 
+/* ---- Optical-flow morph between stills (the reference's optical_flow_morph: scripts/optical_flow_slideshow.py:17-70,
+ * scripts/morph_v2.py:365-468; morph.py).  cv2 absent: every restatement below is parity unpinned. ---- */
+/* cv2.calcOpticalFlowFarneback(prev, next, None, ..., flags) for n independent pairs in the same launches: prev/next
+ * u8 [n,h,w] device, flow f32 [n,h,w,2]; scratch per nst_flow_scratch_floats_ex(n, h, w).  flags = 0 (the box window
+ * of nst_flow_farneback; n = 1 gives its flow bit for bit) or NST_FLOW_GAUSSIAN (cv2.OPTFLOW_FARNEBACK_GAUSSIAN,
+ * FarnebackUpdateFlow_GaussianBlur restated): m = winsize/2 (<= 63), sigma = m*0.3, taps k[0] = 1,
+ * k[i] = (float)exp(-i*i/(2*sigma*sigma)), normalised by s = 1 + 2*sum k[i] in double; the 5 fields of M summed in
+ * fp32 down the columns then along the rows, v = M[y]*k[0], v += (M[y-i] + M[y+i])*k[i] for i = 1..m (replicated
+ * border), and the 2x2 solve in fp32.  Any other flags value -> NST_E_INVALID.  The pyramid's pre-blur takes up to
+ * 511 taps (round(5 sigma) | 1 at the coarsest surviving level; 1080p at 5 or 6 levels needs 77): a deeper one ->
+ * NST_E_SHAPE. */
+#define NST_FLOW_GAUSSIAN 256
+int nst_flow_scratch_floats_ex(int n, int h, int w, size_t* out);
+int nst_flow_farneback_ex(const uint8_t* prev, const uint8_t* next, int n, int h, int w, double pyr_scale, int levels,
+                          int winsize, int iterations, int poly_n, double poly_sigma, int flags, float* flow,
+                          float* scratch, size_t scratch_floats, void* stream);
+/* cv2.cvtColor(img, COLOR_BGR2GRAY) on 8-bit images, here on RGB-ordered frames [n,h,w,3] -> gray [n,h,w]:
+ * (R*9798 + G*19235 + B*3735 + 16384) >> 15.  (nst_gray_u8 is Pillow's luma, what the frame loop uses.) */
+int nst_gray_cv_u8(const uint8_t* rgb, int n, int h, int w, uint8_t* gray, void* stream);
+/* cv2.GaussianBlur(gray, (5, 5), 1.0) of n u8 images [n,h,w] (morph_v2.py:387-388): fp32 taps of
+ * getGaussianKernel(5, 1.0), BORDER_REFLECT_101, rows then columns in fp32, rounded half-to-even to u8.  OpenCV >= 4
+ * blurs u8 images in 8.8 fixed point, so cv2's result may differ from this by 1 grey level (unmeasured).  out != in. */
+int nst_gauss_u8(const uint8_t* in, int n, int h, int w, uint8_t* out, void* stream);
+/* morph_v2.py:405-432 on n flows [n,h,w,2] in place: each component GaussianBlur((15, 15), 3.0) (REFLECT_101,
+ * fp32), then where sqrtf(dx*dx + dy*dy) < 2: dx = (float)(dx + sign*((x - w/2.0)/w)*4.0), dy likewise with y and
+ * h (the sum in double, rounded once).  sign: n host values, +1 (forward flow) or -1 (backward); n <= 16.
+ * scratch: f32 [n,h,w,2]. */
+int nst_morph_flow_post(float* flow, int n, int h, int w, const float* sign, float* scratch, void* stream);
+/* All k frames of one transition in one launch: out u8 [k,h,w,3]; img1/img2 u8 RGB [h,w,3]; flow_fwd/flow_bwd f32
+ * [h,w,2]; t, one_minus_t, wa, wb: k host values each (1 <= k <= NST_MORPH_MAX_FRAMES).  Frame f:
+ *   warped1 = cv2.remap(img1, x + t[f]*fwd.x, y + t[f]*fwd.y, INTER_LINEAR, BORDER_REFLECT)
+ *   warped2 = cv2.remap(img2, x + one_minus_t[f]*bwd.x, y + one_minus_t[f]*bwd.y, INTER_LINEAR, BORDER_REFLECT)
+ *   out[f]  = cv2.addWeighted(warped1, wa[f], warped2, wb[f], 0)
+ * restated: the maps in fp32 (multiply, then add), clamped to [-2w, 3w] x [-2h, 3h] (NaN to the low end) so that no
+ * flow value indexes outside the images; remap in cv2's fixed point (X = rint(mx*32), 5 fraction bits, integer
+ * weights summing to 32768, (sum + 16384) >> 15; each of the four taps reflected on its own, r = p mod 2n,
+ * r < n ? r : 2n-1-r); the blend rint_half_even(p1*wa + p2*wb) in fp32, saturated.  h, w <= 32768. */
+#define NST_MORPH_MAX_FRAMES 128
+int nst_morph_frames(const uint8_t* img1, const uint8_t* img2, const float* flow_fwd, const float* flow_bwd, int h,
+                     int w, int k, const float* t, const float* one_minus_t, const float* wa, const float* wb,
+                     uint8_t* out, void* stream);
+
 /* ---- PNG encode on the owner rank (pipeline.py:2099-2119 `Image.fromarray(out).save(path)`, the reference's
  * default --image_ext png at :2170) ----
  * n u8 frames [n,h,w,c] (c = 1 grey, 3 RGB, 4 RGBA; device) -> n complete PNG files, file j at out + j*out_stride,

@@ -57,7 +57,11 @@ EXPORTED_SYMBOLS = (
     "nst_png_bound", "nst_png_workspace_bytes", "nst_png_encode_u8",
     "nst_jpeg_probe", "nst_jpeg_entropy_decode", "nst_jpeg_workspace_bytes", "nst_jpeg_reconstruct_u8",
     "nst_jpeg_enc_bound", "nst_jpeg_enc_workspace_bytes", "nst_jpeg_encode_u8",
+    "nst_flow_scratch_floats_ex", "nst_flow_farneback_ex", "nst_gray_cv_u8", "nst_gauss_u8", "nst_morph_flow_post",
+    "nst_morph_frames",
 )
+NST_FLOW_GAUSSIAN = 256  # cv2.OPTFLOW_FARNEBACK_GAUSSIAN (nst_flow_farneback_ex flags)
+NST_MORPH_MAX_FRAMES = 128  # frames per nst_morph_frames launch
 NST_E_INVALID, NST_E_SHAPE, NST_E_WORKSPACE, NST_E_DATA = -1, -3, -5, -7
 NST_JPEG_444, NST_JPEG_422, NST_JPEG_420 = 0, 1, 2
 # region compositor limits / geometry kinds (include/nst_hip.h NST_REGION_*, NST_RG_*)
@@ -244,6 +248,15 @@ def lib() -> ctypes.CDLL:
         for name in ("nst_jpeg_probe", "nst_jpeg_entropy_decode", "nst_jpeg_workspace_bytes",
                      "nst_jpeg_reconstruct_u8", "nst_jpeg_enc_bound", "nst_jpeg_enc_workspace_bytes",
                      "nst_jpeg_encode_u8"):
+            getattr(L, name).restype = i
+        L.nst_flow_scratch_floats_ex.argtypes = [i, i, i, psz]
+        L.nst_flow_farneback_ex.argtypes = [vp, vp, i, i, i, dbl, i, i, i, i, dbl, i, vp, vp, sz, vp]
+        L.nst_gray_cv_u8.argtypes = [vp, i, i, i, vp, vp]
+        L.nst_gauss_u8.argtypes = [vp, i, i, i, vp, vp]
+        L.nst_morph_flow_post.argtypes = [vp, i, i, i, pf, vp, vp]
+        L.nst_morph_frames.argtypes = [vp, vp, vp, vp, i, i, i, pf, pf, pf, pf, vp, vp]
+        for name in ("nst_flow_scratch_floats_ex", "nst_flow_farneback_ex", "nst_gray_cv_u8", "nst_gauss_u8",
+                     "nst_morph_flow_post", "nst_morph_frames"):
             getattr(L, name).restype = i
         for name in ("nst_png_bound", "nst_png_workspace_bytes", "nst_png_encode_u8"):
             getattr(L, name).restype = i

@@ -118,4 +118,89 @@ int nst_motion_alpha(const float* flow, int h, int w, float motion_norm, double 
   return NST_OK;
 }
 
+// ---- optical-flow morph (include/nst_hip.h "Optical-flow morph between stills") ----
+int nst_flow_scratch_floats_ex(int n, int h, int w, size_t* out) {
+  if (n <= 0 || n > 64 || h <= 0 || w <= 0 || !out) {
+    set_error("nst_flow_scratch_floats_ex: invalid arguments (1 <= n <= 64)");
+    return NST_E_INVALID;
+  }
+  *out = farneback_scratch_floats_ex(n, h, w);
+  return NST_OK;
+}
+
+int nst_flow_farneback_ex(const uint8_t* prev, const uint8_t* next, int n, int h, int w, double pyr_scale, int levels,
+                          int winsize, int iterations, int poly_n, double poly_sigma, int flags, float* flow,
+                          float* scratch, size_t scratch_floats, void* stream) {
+  if (flags != 0 && flags != NST_FLOW_GAUSSIAN) {
+    set_error("nst_flow_farneback_ex: flags must be 0 or NST_FLOW_GAUSSIAN (256), got " + std::to_string(flags));
+    return NST_E_INVALID;
+  }
+  if (!prev || !next || !flow || !scratch || n < 1 || n > 64 || h < 2 || w < 2 || h > 65535 ||
+      !(pyr_scale > 0 && pyr_scale < 1) || levels < 0 || winsize < 1 || (winsize & 1) == 0 || iterations < 1 ||
+      poly_n < 1 || poly_n > 8 || (flags == NST_FLOW_GAUSSIAN && winsize / 2 > 63) ||
+      scratch_floats < farneback_scratch_floats_ex(n, h, w)) {
+    set_error("nst_flow_farneback_ex: invalid arguments (1 <= n <= 64, odd winsize, at most 127 with the Gaussian "
+              "window, poly_n 1..8, scratch per nst_flow_scratch_floats_ex)");
+    return NST_E_INVALID;
+  }
+  const int ksz = farneback_max_ksize(h, w, pyr_scale, levels);
+  if (ksz > 511) {
+    set_error("nst_flow_farneback_ex: the pyramid of a " + std::to_string(w) + "x" + std::to_string(h) + " frame at " +
+              std::to_string(levels) + " levels needs a " + std::to_string(ksz) + "-tap pre-blur (at most 511)");
+    return NST_E_SHAPE;
+  }
+  FL_LAUNCH(launch_farneback_ex(prev, next, n, h, w, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma,
+                                flags == NST_FLOW_GAUSSIAN, flow, scratch, (hipStream_t)stream),
+            "farneback_ex");
+  return NST_OK;
+}
+
+int nst_gray_cv_u8(const uint8_t* rgb, int n, int h, int w, uint8_t* gray, void* stream) {
+  if (!rgb || !gray || n <= 0 || h <= 0 || w <= 0) { set_error("nst_gray_cv_u8: invalid arguments"); return NST_E_INVALID; }
+  FL_LAUNCH(launch_gray_cv(rgb, (size_t)n * h * w, gray, (hipStream_t)stream), "gray_cv");
+  return NST_OK;
+}
+
+int nst_gauss_u8(const uint8_t* in, int n, int h, int w, uint8_t* out, void* stream) {
+  if (!in || !out || in == out || n <= 0 || n > 65535 || h <= 0 || w <= 0) {
+    set_error("nst_gauss_u8: invalid arguments (out != in, n <= 65535)");
+    return NST_E_INVALID;
+  }
+  FL_LAUNCH(launch_gauss_u8(in, n, h, w, out, (hipStream_t)stream), "gauss_u8");
+  return NST_OK;
+}
+
+int nst_morph_flow_post(float* flow, int n, int h, int w, const float* sign, float* scratch, void* stream) {
+  if (!flow || !sign || !scratch || scratch == flow || n <= 0 || n > 16 || h <= 0 || w <= 0) {
+    set_error("nst_morph_flow_post: invalid arguments (1 <= n <= 16, scratch != flow)");
+    return NST_E_INVALID;
+  }
+  for (int i = 0; i < n; ++i)
+    if (sign[i] != 1.f && sign[i] != -1.f) {
+      set_error("nst_morph_flow_post: sign must be +1 or -1");
+      return NST_E_INVALID;
+    }
+  FL_LAUNCH(launch_morph_flow_post(flow, n, h, w, sign, scratch, (hipStream_t)stream), "morph_flow_post");
+  return NST_OK;
+}
+
+int nst_morph_frames(const uint8_t* img1, const uint8_t* img2, const float* flow_fwd, const float* flow_bwd, int h,
+                     int w, int k, const float* t, const float* one_minus_t, const float* wa, const float* wb,
+                     uint8_t* out, void* stream) {
+  if (!img1 || !img2 || !flow_fwd || !flow_bwd || !t || !one_minus_t || !wa || !wb || !out || k < 1 ||
+      k > NST_MORPH_MAX_FRAMES || ((uintptr_t)flow_fwd & 7) || ((uintptr_t)flow_bwd & 7)) {
+    set_error("nst_morph_frames: invalid arguments (1 <= k <= " + std::to_string(NST_MORPH_MAX_FRAMES) +
+              ", flows 8-byte aligned)");
+    return NST_E_INVALID;
+  }
+  if (h < 1 || w < 1 || h > 32768 || w > 32768) {
+    set_error("nst_morph_frames: frame " + std::to_string(w) + "x" + std::to_string(h) + " outside 1..32768");
+    return NST_E_SHAPE;
+  }
+  FL_LAUNCH(launch_morph_frames(img1, img2, flow_fwd, flow_bwd, h, w, k, t, one_minus_t, wa, wb, out,
+                                (hipStream_t)stream),
+            "morph_frames");
+  return NST_OK;
+}
+
 }  // extern "C"

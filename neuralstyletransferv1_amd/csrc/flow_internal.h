@@ -27,5 +27,22 @@ hipError_t launch_flow_fuse(const float* curr, const float* prev, const float* f
                             float* out, hipStream_t st);
 hipError_t launch_motion_alpha(const float* flow, int h, int w, float norm, double sigma, float max_alpha, float span,
                                float* alpha, float* tmp, hipStream_t st);
+// Farneback for n pairs in the same launches (prev/next [n,h,w], flow [n,h,w,2]); gaussian: the Gaussian window
+// (OPTFLOW_FARNEBACK_GAUSSIAN, winsize / 2 <= 63) instead of the box
+size_t farneback_scratch_floats_ex(int n, int h, int w);
+hipError_t launch_farneback_ex(const uint8_t* prev, const uint8_t* next, int n, int h, int w, double pyr_scale,
+                               int levels, int winsize, int iterations, int poly_n, double poly_sigma, bool gaussian,
+                               float* flow, float* scratch, hipStream_t st);
+// the widest pyramid pre-blur (taps) launch_farneback_ex would run for these arguments; it takes at most 511
+int farneback_max_ksize(int h, int w, double pyr_scale, int levels);
+// cv2.getGaussianKernel(n, sigma, CV_32F) into t[n] (n <= 63)
+void gaussian_taps_f32(int n, double sigma, float* t);
+// morph_ops.hip
+hipError_t launch_gray_cv(const uint8_t* rgb, size_t npix, uint8_t* gray, hipStream_t st);
+hipError_t launch_gauss_u8(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st);
+hipError_t launch_morph_flow_post(float* flow, int n, int h, int w, const float* sign, float* scratch, hipStream_t st);
+hipError_t launch_morph_frames(const uint8_t* img1, const uint8_t* img2, const float* fwd, const float* bwd, int h,
+                               int w, int k, const float* t, const float* omt, const float* wa, const float* wb,
+                               uint8_t* out, hipStream_t st);
 
 }  // namespace nst

@@ -575,4 +575,358 @@ hipError_t launch_motion_alpha(const float* flow, int h, int w, float norm, doub
   return hipGetLastError();
 }
 
+void gaussian_taps_f32(int n, double sigma, float* t) {
+  const Taps tp = gaussian_taps(n, sigma);
+  for (int i = 0; i < n; ++i) t[i] = tp.t[i];
+}
+
+// ---- Farneback for n pairs in the same launches (nst_flow_farneback_ex; the morph's forward and backward flows
+// are n = 2 with the images swapped).  The image planes are [prev_0 .. prev_n-1, next_0 .. next_n-1], so that the
+// blur, the resize and PolyExp above take them as 2n planes; the three kernels below are the single-pair
+// UpdateMatrices and box kernels with the pair in blockIdx.z (same arithmetic, same order: n = 1 is bit-identical to
+// launch_farneback). ----
+__global__ __launch_bounds__(256) void update_matrices_n_kernel(const float* __restrict__ R, const float* __restrict__ flow_n,
+                                                                int n, int h, int w, float* __restrict__ M_n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t hw = (size_t)h * w;
+  if (i >= hw) return;
+  const float* R0 = R + (size_t)blockIdx.z * hw * 5;
+  const float* R1 = R + ((size_t)n + blockIdx.z) * hw * 5;
+  const float* flow = flow_n + (size_t)blockIdx.z * hw * 2;
+  float* M = M_n + (size_t)blockIdx.z * hw * 5;
+  const int x = (int)(i % w), y = (int)(i / w);
+  const float border[5] = {0.14f, 0.14f, 0.4472f, 0.4472f, 0.4472f};
+  const float dx = flow[2 * i], dy = flow[2 * i + 1];
+  float fx = (float)x + dx, fy = (float)y + dy;
+  // a non-finite flow (a degenerate solve) would make the int conversion undefined: such a pixel takes the
+  // outside branch, as any position outside the frame does
+  const bool fin = fabsf(fx) < 1e9f && fabsf(fy) < 1e9f;
+  const int x1 = fin ? (int)floorf(fx) : -1, y1 = fin ? (int)floorf(fy) : -1;
+  fx -= (float)x1;
+  fy -= (float)y1;
+  const float* r0 = R0 + i * 5;
+  float r2, r3, r4, r5, r6;
+  if ((unsigned)x1 < (unsigned)(w - 1) && (unsigned)y1 < (unsigned)(h - 1)) {
+    const float a00 = (1.f - fx) * (1.f - fy), a01 = fx * (1.f - fy), a10 = (1.f - fx) * fy, a11 = fx * fy;
+    const float* p = R1 + ((size_t)y1 * w + x1) * 5;
+    const size_t s1 = (size_t)w * 5;
+    float v[5];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) v[c] = a00 * p[c] + a01 * p[5 + c] + a10 * p[s1 + c] + a11 * p[s1 + 5 + c];
+    r2 = v[0]; r3 = v[1];
+    r4 = (r0[2] + v[2]) * 0.5f;
+    r5 = (r0[3] + v[3]) * 0.5f;
+    r6 = (r0[4] + v[4]) * 0.25f;
+  } else {
+    r2 = r3 = 0.f;
+    r4 = r0[2];
+    r5 = r0[3];
+    r6 = r0[4] * 0.5f;
+  }
+  r2 = (r0[0] - r2) * 0.5f;
+  r3 = (r0[1] - r3) * 0.5f;
+  r2 += r4 * dy + r6 * dx;
+  r3 += r6 * dy + r5 * dx;
+  if ((unsigned)(x - 5) >= (unsigned)(w - 10) || (unsigned)(y - 5) >= (unsigned)(h - 10)) {
+    const float sc = (x < 5 ? border[x] : 1.f) * (x >= w - 5 ? border[w - x - 1] : 1.f) * (y < 5 ? border[y] : 1.f) *
+                     (y >= h - 5 ? border[h - y - 1] : 1.f);
+    r2 *= sc; r3 *= sc; r4 *= sc; r5 *= sc; r6 *= sc;
+  }
+  float* m = M + i * 5;
+  m[0] = r4 * r4 + r6 * r6;
+  m[1] = (r4 + r5) * r6;
+  m[2] = r5 * r5 + r6 * r6;
+  m[3] = r4 * r2 + r6 * r3;
+  m[4] = r6 * r2 + r5 * r3;
+}
+
+__global__ __launch_bounds__(256) void box_v_n_kernel(const float* __restrict__ M_n, int h, int w, int m,
+                                                      double* __restrict__ vs_n) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= w) return;
+  const float* M = M_n + (size_t)blockIdx.z * h * w * 5;
+  double* vs = vs_n + (size_t)blockIdx.z * h * w * 5;
+  const int y0 = blockIdx.y * BOX_ROWS, y1 = min(h, y0 + BOX_ROWS);
+  auto row = [&](int q) { return M + ((size_t)min(max(q, 0), h - 1) * w + x) * 5; };
+  double s[5] = {0, 0, 0, 0, 0};
+  for (int q = y0 - m; q <= y0 + m; ++q) {
+    const float* p = row(q);
+#pragma unroll
+    for (int c = 0; c < 5; ++c) s[c] += p[c];
+  }
+  for (int y = y0; y < y1; ++y) {
+    if (y > y0) {
+      const float* pa = row(y + m);
+      const float* pd = row(y - m - 1);
+#pragma unroll
+      for (int c = 0; c < 5; ++c) s[c] += pa[c] - pd[c];
+    }
+    double* o = vs + ((size_t)y * w + x) * 5;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) o[c] = s[c];
+  }
+}
+
+__global__ __launch_bounds__(256) void box_h_solve_n_kernel(const double* __restrict__ vs_n, int h, int w, int m,
+                                                            double scale, float* __restrict__ flow_n) {
+  extern __shared__ double seg[];  // (256 + 2m) x 5
+  const double* vs = vs_n + (size_t)blockIdx.z * h * w * 5;
+  float* flow = flow_n + (size_t)blockIdx.z * h * w * 2;
+  const int y = blockIdx.y, x0 = blockIdx.x * 256;
+  const int n = 256 + 2 * m;
+  for (int j = threadIdx.x; j < n * 5; j += 256) {
+    const int e = j / 5, c = j - e * 5;
+    const int xs = min(max(x0 - m + e, 0), w - 1);
+    seg[j] = vs[((size_t)y * w + xs) * 5 + c];
+  }
+  __syncthreads();
+  const int x = x0 + threadIdx.x;
+  if (x >= w) return;
+  double s[5] = {0, 0, 0, 0, 0};
+  for (int q = 0; q <= 2 * m; ++q) {
+    const double* p = seg + (threadIdx.x + q) * 5;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) s[c] += p[c];
+  }
+  const size_t i = (size_t)y * w + x;
+  const double g11 = s[0] * scale, g12 = s[1] * scale, g22 = s[2] * scale, h1 = s[3] * scale, h2 = s[4] * scale;
+  const double idet = 1. / (g11 * g22 - g12 * g12 + 1e-3);
+  flow[2 * i] = (float)((g11 * h2 - g12 * h1) * idet);
+  flow[2 * i + 1] = (float)((g22 * h1 - g12 * h2) * idet);
+}
+
+// FarnebackUpdateFlow_GaussianBlur (OPTFLOW_FARNEBACK_GAUSSIAN): the window is a separable Gaussian of half-width
+// m, all in fp32 (the translation unit is built with -ffp-contract=off: every product and sum below rounds on its
+// own, in the order written).  Vertical pass: one thread per pixel, rows clamped to the frame.
+struct WinTaps {
+  int m;
+  float k[64];  // k[0 .. m]
+};
+
+// OpenCV's tap rule: sigma = m * 0.3, k[0] = 1, k[i] = (float)exp(-i*i / (2 sigma^2)); s = 1 + 2 sum k[i] in
+// double; k[i] = (float)(k[i] / s)
+static WinTaps window_taps(int m) {
+  WinTaps t;
+  t.m = m;
+  const double sigma = m * 0.3;
+  double s = 1;
+  t.k[0] = 1.f;
+  for (int i = 1; i <= m; ++i) {
+    t.k[i] = (float)std::exp(-i * i / (2 * sigma * sigma));
+    s += 2.0 * t.k[i];
+  }
+  for (int i = 0; i <= m; ++i) t.k[i] = (float)(t.k[i] / s);
+  return t;
+}
+
+__global__ __launch_bounds__(256) void gwin_v_kernel(const float* __restrict__ M_n, int h, int w, WinTaps tp,
+                                                     float* __restrict__ vs_n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t hw = (size_t)h * w;
+  if (i >= hw) return;
+  const float* M = M_n + (size_t)blockIdx.z * hw * 5;
+  const int x = (int)(i % w), y = (int)(i / w);
+  const float* c0 = M + i * 5;
+  float v[5];
+#pragma unroll
+  for (int c = 0; c < 5; ++c) v[c] = c0[c] * tp.k[0];
+  for (int q = 1; q <= tp.m; ++q) {
+    const float* a = M + ((size_t)max(y - q, 0) * w + x) * 5;
+    const float* b = M + ((size_t)min(y + q, h - 1) * w + x) * 5;
+    const float kq = tp.k[q];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) v[c] = v[c] + (a[c] + b[c]) * kq;
+  }
+  float* o = vs_n + ((size_t)blockIdx.z * hw + i) * 5;
+#pragma unroll
+  for (int c = 0; c < 5; ++c) o[c] = v[c];
+}
+
+// horizontal pass over the vertical sums (a 256-pixel row segment and its halo staged in LDS, columns clamped to
+// the frame) and the 2x2 solve, in fp32
+__global__ __launch_bounds__(256) void gwin_h_solve_kernel(const float* __restrict__ vs_n, int h, int w, WinTaps tp,
+                                                           float* __restrict__ flow_n) {
+  extern __shared__ float fseg[];  // (256 + 2m) x 5
+  const float* vs = vs_n + (size_t)blockIdx.z * h * w * 5;
+  float* flow = flow_n + (size_t)blockIdx.z * h * w * 2;
+  const int y = blockIdx.y, x0 = blockIdx.x * 256, m = tp.m;
+  const int n = 256 + 2 * m;
+  for (int j = threadIdx.x; j < n * 5; j += 256) {
+    const int e = j / 5, c = j - e * 5;
+    const int xs = min(max(x0 - m + e, 0), w - 1);
+    fseg[j] = vs[((size_t)y * w + xs) * 5 + c];
+  }
+  __syncthreads();
+  const int x = x0 + threadIdx.x;
+  if (x >= w) return;
+  const float* c0 = fseg + (threadIdx.x + m) * 5;
+  float s[5];
+#pragma unroll
+  for (int c = 0; c < 5; ++c) s[c] = c0[c] * tp.k[0];
+  for (int q = 1; q <= m; ++q) {
+    const float* a = c0 - q * 5;
+    const float* b = c0 + q * 5;
+    const float kq = tp.k[q];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) s[c] = s[c] + (a[c] + b[c]) * kq;
+  }
+  const size_t i = (size_t)y * w + x;
+  const float g11 = s[0], g12 = s[1], g22 = s[2], h1 = s[3], h2 = s[4];
+  const float idet = 1.f / (g11 * g22 - g12 * g12 + 1e-3f);
+  flow[2 * i] = (g11 * h2 - g12 * h1) * idet;
+  flow[2 * i + 1] = (g22 * h1 - g12 * h2) * idet;
+}
+
+// The pyramid's pre-blur grows with the depth (ksize = round(5 sigma) | 1, sigma = (1 / scale - 1) / 2): the morph's 5
+// and 6 levels reach 77 taps at 1080p, past launch_gauss's 63.  Same kernels with a table of up to 511 taps (the
+// same accumulation order), used for the levels that need it.
+constexpr int WIDE_TAPS = 511;
+struct WideTaps {
+  int n;
+  float t[WIDE_TAPS];
+};
+
+__global__ __launch_bounds__(256) void gauss_rows_wide_kernel(const float* __restrict__ in, int h, int w, WideTaps tp,
+                                                              float* __restrict__ out) {
+  const size_t plane = (size_t)blockIdx.z * h * w;
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= w) return;
+  const int r = tp.n / 2;
+  const float* row = in + plane + (size_t)y * w;
+  float acc = 0.f;
+  for (int j = 0; j < tp.n; ++j) acc = acc + tp.t[j] * row[refl101(x + j - r, w)];
+  out[plane + (size_t)y * w + x] = acc;
+}
+
+__global__ __launch_bounds__(256) void gauss_cols_wide_kernel(const float* __restrict__ in, int h, int w, WideTaps tp,
+                                                              float* __restrict__ out) {
+  const size_t plane = (size_t)blockIdx.z * h * w;
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= w) return;
+  const int r = tp.n / 2;
+  float acc = 0.f;
+  for (int j = 0; j < tp.n; ++j) acc = acc + tp.t[j] * in[plane + (size_t)refl101(y + j - r, h) * w + x];
+  out[plane + (size_t)y * w + x] = acc;
+}
+
+static hipError_t launch_gauss_wide(float* planes, int k, int h, int w, int ksize, double sigma, float* tmp,
+                                    hipStream_t st) {
+  if (ksize <= 63) return launch_gauss(planes, k, h, w, ksize, sigma, tmp, st);
+  if (ksize > WIDE_TAPS) return hipErrorInvalidValue;
+  WideTaps tp;  // cv2.getGaussianKernel(ksize, sigma > 0, CV_32F), as gaussian_taps
+  tp.n = ksize;
+  const double s2 = -0.5 / (sigma * sigma);
+  double sum = 0;
+  double v[WIDE_TAPS];
+  for (int i = 0; i < ksize; ++i) {
+    const double x = i - (ksize - 1) * 0.5;
+    v[i] = std::exp(s2 * x * x);
+    sum += v[i];
+  }
+  for (int i = 0; i < WIDE_TAPS; ++i) tp.t[i] = i < ksize ? (float)(v[i] / sum) : 0.f;
+  const dim3 g((unsigned)((w + 255) / 256), (unsigned)h, (unsigned)k);
+  hipLaunchKernelGGL(gauss_rows_wide_kernel, g, dim3(256), 0, st, planes, h, w, tp, tmp);
+  hipLaunchKernelGGL(gauss_cols_wide_kernel, g, dim3(256), 0, st, tmp, h, w, tp, planes);
+  return hipGetLastError();
+}
+
+// the widest pre-blur of the pyramid launch_farneback_ex would run (its level rule), for the entry point's check
+int farneback_max_ksize(int h, int w, double pyr_scale, int levels) {
+  int k;
+  double scale = 1;
+  for (k = 0; k < levels; ++k) {
+    scale *= pyr_scale;
+    if (w * scale < 32 || h * scale < 32) break;
+  }
+  scale = 1;
+  for (int i = 0; i < k; ++i) scale *= pyr_scale;
+  const double sigma = (1. / scale - 1) * 0.5;
+  return std::max(((int)std::nearbyint(sigma * 5)) | 1, 3);
+}
+
+size_t farneback_scratch_floats_ex(int n, int h, int w) {
+  // per pair what farneback_scratch_floats counts (the + 64 covers the padding before the 8-byte-aligned window sums)
+  return (size_t)n * h * w * (2 + 2 + 2 + 6 + 10 + 5 + 10 + 4) + 64;
+}
+
+hipError_t launch_farneback_ex(const uint8_t* prev, const uint8_t* next, int np, int h, int w, double pyr_scale,
+                               int levels, int winsize, int iterations, int poly_n, double poly_sigma, bool gaussian,
+                               float* flow_out, float* scratch, hipStream_t st) {
+  const size_t n = (size_t)h * w, N = n * np;
+  float* img = scratch;             // 2 np planes, full resolution: prev_0 .. prev_np-1, next_0 .. next_np-1
+  float* tmp = img + 2 * N;         // 2 np planes
+  float* I = tmp + 2 * N;           // 2 np planes at the level size
+  float* row3 = I + 2 * N;          // 2 np x 3ch
+  float* R = row3 + 6 * N;          // 2 np x 5ch (R0 of pair p: plane p, R1: plane np + p)
+  float* M = R + 10 * N;            // np x 5ch
+  double* vs = (double*)(M + 5 * N + ((5 * N) & 1));  // np x 5 doubles per pixel (fp32 sums for the Gaussian window)
+  float* fa = (float*)(vs + 5 * N); // np x 2ch
+  float* fb = fa + 2 * N;           // np x 2ch
+  const int min_size = 32;
+  int k;
+  double scale = 1;
+  for (k = 0; k < levels; ++k) {
+    scale *= pyr_scale;
+    if (w * scale < min_size || h * scale < min_size) break;
+  }
+  levels = k;
+  const PolyTab pt = poly_tab(poly_n, poly_sigma);
+  const int m = winsize / 2;
+  const double bscale = 1. / ((double)winsize * winsize);
+  WinTaps wt;
+  wt.m = 0;
+  if (gaussian) wt = window_taps(m);
+  float* prev_flow = nullptr;
+  int pw = 0, ph = 0;
+  for (k = levels; k >= 0; --k) {
+    scale = 1;
+    for (int i = 0; i < k; ++i) scale *= pyr_scale;
+    const double sigma = (1. / scale - 1) * 0.5;
+    int ksz = ((int)std::nearbyint(sigma * 5)) | 1;
+    ksz = std::max(ksz, 3);
+    const int lw = (int)std::nearbyint(w * scale), lh = (int)std::nearbyint(h * scale);
+    const size_t ln = (size_t)lw * lh;
+    float* flow = k == 0 ? flow_out : (prev_flow == fa ? fb : fa);
+    hipError_t e;
+    if (!prev_flow) {
+      e = hipMemsetAsync(flow, 0, ln * np * 2 * sizeof(float), st);
+    } else {
+      e = launch_resize_lin(prev_flow, np, ph, pw, 2, lh, lw, (float)(1. / pyr_scale), flow, st);
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(u8_to_f32_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, prev, N, img);
+    hipLaunchKernelGGL(u8_to_f32_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, next, N, img + N);
+    e = launch_gauss_wide(img, 2 * np, h, w, ksz, sigma, tmp, st);
+    if (e != hipSuccess) return e;
+    const float* lev = img;
+    if (lw != w || lh != h) {
+      e = launch_resize_lin(img, 2 * np, h, w, 1, lh, lw, 1.f, I, st);
+      if (e != hipSuccess) return e;
+      lev = I;
+    }
+    const dim3 gl((unsigned)((ln + 255) / 256), 1, 2 * (unsigned)np);
+    hipLaunchKernelGGL(polyexp_v_kernel, gl, dim3(256), 0, st, lev, lh, lw, pt, row3);
+    hipLaunchKernelGGL(polyexp_h_kernel, gl, dim3(256), 0, st, row3, lh, lw, pt, R);
+    const dim3 g1((unsigned)((ln + 255) / 256), 1, (unsigned)np);
+    hipLaunchKernelGGL(update_matrices_n_kernel, g1, dim3(256), 0, st, R, flow, np, lh, lw, M);
+    const dim3 gv((unsigned)((lw + 255) / 256), (unsigned)((lh + BOX_ROWS - 1) / BOX_ROWS), (unsigned)np);
+    const dim3 gh((unsigned)((lw + 255) / 256), (unsigned)lh, (unsigned)np);
+    const size_t hl = (size_t)(256 + 2 * m) * 5 * (gaussian ? sizeof(float) : sizeof(double));
+    for (int it = 0; it < iterations; ++it) {
+      if (gaussian) {
+        hipLaunchKernelGGL(gwin_v_kernel, g1, dim3(256), 0, st, M, lh, lw, wt, (float*)vs);
+        hipLaunchKernelGGL(gwin_h_solve_kernel, gh, dim3(256), hl, st, (const float*)vs, lh, lw, wt, flow);
+      } else {
+        hipLaunchKernelGGL(box_v_n_kernel, gv, dim3(256), 0, st, M, lh, lw, m, vs);
+        hipLaunchKernelGGL(box_h_solve_n_kernel, gh, dim3(256), hl, st, vs, lh, lw, m, bscale, flow);
+      }
+      if (it < iterations - 1) hipLaunchKernelGGL(update_matrices_n_kernel, g1, dim3(256), 0, st, R, flow, np, lh, lw, M);
+    }
+    prev_flow = flow;
+    pw = lw;
+    ph = lh;
+  }
+  return hipGetLastError();
+}
+
 }  // namespace nst

@@ -1,0 +1,348 @@
+"""Optical-flow morph between stills on the MI355X engine: the reference's `optical_flow_morph`
+(scripts/optical_flow_slideshow.py:17-70, scripts/morph_v2.py:365-468 and the copies in morph_faces.py,
+generate_morph_samples.py and the optical_flow_* batch scripts) and a CLI that turns a list of stills into the
+frames of a morphing slideshow.
+
+Per transition img1 -> img2 (RGB uint8 device tensors of one size):
+  gray = cv2.cvtColor(img, COLOR_BGR2GRAY)                          nst_gray_cv_u8
+  gray = cv2.GaussianBlur(gray, (5, 5), 1.0)          (preset v2)   nst_gauss_u8
+  fwd, bwd = cv2.calcOpticalFlowFarneback(g1, g2 | g2, g1, ..., OPTFLOW_FARNEBACK_GAUSSIAN)
+                                                                    nst_flow_farneback_ex, n = 2 in the same launches
+  blur 15x15 sigma 3 + radial minimum flow            (preset v2)   nst_morph_flow_post
+  k frames: two cv2.remap(INTER_LINEAR, BORDER_REFLECT) + cv2.addWeighted
+                                                                    nst_morph_frames, all frames of a launch at once
+
+Presets (the reference's two parameter sets):
+  slideshow  Farneback 0.5 / 5 / 15 / 3 / 7 / 1.5, no pre-blur, no post-processing, t = alpha = i / (k - 1)
+  v2         pre-blur, Farneback 0.5 / 6 / 21 / 5 / 7 / 1.5, flow post-processing, t = ease(i / (k - 1)) with
+             ease in linear | smooth (cubic in/out) | smoother (smootherstep), alpha = smoothstep(i / (k - 1))
+k = 1 gives t = 0 in both.  The schedules are computed in double and rounded once to the fp32 the kernel multiplies
+by (t, 1 - t, 1 - alpha, alpha).
+
+Stills are decoded with Pillow and fitted by cover + centre crop with morph_v2.py:704-712's sizes (int(w * scale),
+(new - target) // 2); the resize is the engine's Pillow-exact LANCZOS (Image.resize(LANCZOS)) and REPLACES the
+reference's cv2.INTER_LANCZOS4 (an 8-tap kernel without Pillow's support scaling): fitted stills differ from the
+reference's.  cv2 is not installed in this environment, so the grey, blur, Farneback, remap and addWeighted
+restatements are parity unpinned; tests/morph_ref.py is their numpy yardstick.
+
+Out of scope (not built): morph_v2's Ken Burns pan / zoom, zoom pulse, hue rotation and temporal_smooth_frames (its
+float promotion depends on the numpy version, and it truncates), its DeepLab and Magenta orchestration, and
+morph_faces.py's face detection.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import sys
+from pathlib import Path
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import NstError, check, lib
+
+# pyr_scale, levels, winsize, iterations, poly_n, poly_sigma
+PRESETS = {
+    "slideshow": dict(farneback=(0.5, 5, 15, 3, 7, 1.5), pre_blur=False, post=False),
+    "v2": dict(farneback=(0.5, 6, 21, 5, 7, 1.5), pre_blur=True, post=True),
+}
+EASINGS = ("linear", "smooth", "smoother")
+IMAGE_PATTERNS = ("*.jpg", "*.jpeg", "*.png")
+
+
+def ease_in_out_cubic(t: float) -> float:
+    return 4 * t * t * t if t < 0.5 else 1 - pow(-2 * t + 2, 3) / 2
+
+
+def smoothstep(t: float) -> float:
+    return t * t * (3 - 2 * t)
+
+
+def smootherstep(t: float) -> float:
+    return t * t * t * (t * (6 * t - 15) + 10)
+
+
+_EASE = {"linear": lambda t: t, "smooth": ease_in_out_cubic, "smoother": smootherstep}
+
+
+def schedule(k: int, preset: str = "v2", easing: str = "smooth") -> Tuple[np.ndarray, np.ndarray]:
+    """(t, alpha) of the k frames of a transition, float64."""
+    if preset not in PRESETS:
+        raise ValueError(f"preset must be one of {sorted(PRESETS)}, got {preset!r}")
+    if easing not in _EASE:
+        raise ValueError(f"easing must be one of {EASINGS}, got {easing!r}")
+    if k < 1:
+        raise ValueError(f"a transition needs at least one frame, got {k}")
+    lin = [i / (k - 1) if k > 1 else 0.0 for i in range(k)]
+    if preset == "slideshow":
+        return np.array(lin, np.float64), np.array(lin, np.float64)
+    return np.array([_EASE[easing](x) for x in lin], np.float64), np.array([smoothstep(x) for x in lin], np.float64)
+
+
+def kernel_schedule(t: np.ndarray, alpha: np.ndarray):
+    """The four fp32 rows nst_morph_frames takes: t, 1 - t, 1 - alpha, alpha (each computed in double, rounded once)."""
+    return (t.astype(np.float32), (1.0 - t).astype(np.float32), (1.0 - alpha).astype(np.float32),
+            alpha.astype(np.float32))
+
+
+def _u8(x: torch.Tensor, what: str, dims: int) -> torch.Tensor:
+    _lib.require_gpu_tensor(x, what)
+    if x.dtype != torch.uint8 or x.dim() != dims:
+        raise NstError(f"{what}: expected a uint8 tensor of {dims} dimensions, got {x.dtype} {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def gray_cv_u8(frames_u8: torch.Tensor) -> torch.Tensor:
+    """[n,h,w,3] uint8 RGB -> [n,h,w] uint8, cv2's 8-bit COLOR_BGR2GRAY weights."""
+    x = _u8(frames_u8, "gray_cv_u8 frames", 4)
+    n, h, w, _ = x.shape
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=x.device)
+    check(lib().nst_gray_cv_u8(x.data_ptr(), n, h, w, out.data_ptr(), _lib.stream_ptr(x.device)), "nst_gray_cv_u8")
+    return out
+
+
+def gauss_u8(gray: torch.Tensor) -> torch.Tensor:
+    """[n,h,w] uint8 -> cv2.GaussianBlur(g, (5, 5), 1.0) restated in fp32."""
+    x = _u8(gray, "gauss_u8 images", 3)
+    n, h, w = x.shape
+    out = torch.empty_like(x)
+    check(lib().nst_gauss_u8(x.data_ptr(), n, h, w, out.data_ptr(), _lib.stream_ptr(x.device)), "nst_gauss_u8")
+    return out
+
+
+def farneback_ex(prev: torch.Tensor, nxt: torch.Tensor, params, flags: int = 0) -> torch.Tensor:
+    """n pairs [n,h,w] uint8 x 2 -> flows [n,h,w,2] float32 in the same launches; flags 0 or NST_FLOW_GAUSSIAN."""
+    p, q = _u8(prev, "farneback_ex prev", 3), _u8(nxt, "farneback_ex next", 3)
+    if p.shape != q.shape:
+        raise NstError(f"farneback_ex: shapes differ, {tuple(p.shape)} and {tuple(q.shape)}")
+    n, h, w = p.shape
+    dev = p.device
+    sz = ctypes.c_size_t()
+    check(lib().nst_flow_scratch_floats_ex(n, h, w, ctypes.byref(sz)), "nst_flow_scratch_floats_ex")
+    sc = torch.empty((sz.value,), dtype=torch.float32, device=dev)
+    flow = torch.empty((n, h, w, 2), dtype=torch.float32, device=dev)
+    ps, lv, ws, it, pn, sg = params
+    check(lib().nst_flow_farneback_ex(p.data_ptr(), q.data_ptr(), n, h, w, float(ps), int(lv), int(ws), int(it), int(pn),
+                                      float(sg), int(flags), flow.data_ptr(), sc.data_ptr(), sc.numel(),
+                                      _lib.stream_ptr(dev)), "nst_flow_farneback_ex")
+    sc.record_stream(torch.cuda.current_stream(dev))
+    return flow
+
+
+def flow_post(flow: torch.Tensor, signs: Sequence[float]) -> torch.Tensor:
+    """morph_v2.py:405-432 on flows [n,h,w,2] (a copy is returned): blur, then the radial term with signs[n]."""
+    _lib.require_gpu_tensor(flow, "flow_post flow")
+    if flow.dtype != torch.float32 or flow.dim() != 4 or flow.shape[3] != 2 or len(signs) != flow.shape[0]:
+        raise NstError(f"flow_post: expected float32 [n,h,w,2] and n signs, got {flow.dtype} {tuple(flow.shape)}")
+    out = flow.contiguous().clone()
+    n, h, w, _ = out.shape
+    scratch = torch.empty_like(out)
+    sg = (ctypes.c_float * n)(*[float(s) for s in signs])
+    check(lib().nst_morph_flow_post(out.data_ptr(), n, h, w, sg, scratch.data_ptr(), _lib.stream_ptr(out.device)),
+          "nst_morph_flow_post")
+    scratch.record_stream(torch.cuda.current_stream(out.device))
+    return out
+
+
+def morph_frames(img1: torch.Tensor, img2: torch.Tensor, fwd: torch.Tensor, bwd: torch.Tensor, t: np.ndarray,
+                 alpha: np.ndarray, batch: Optional[int] = None) -> torch.Tensor:
+    """The frames of a transition, uint8 [k,h,w,3]: `batch` frames per nst_morph_frames launch (default: as many as
+    one launch takes)."""
+    a, b = _u8(img1, "morph_frames img1", 3), _u8(img2, "morph_frames img2", 3)
+    h, w, c = a.shape
+    if c != 3 or b.shape != a.shape:
+        raise NstError(f"morph_frames: images must both be [h,w,3], got {tuple(a.shape)} and {tuple(b.shape)}")
+    for f in (fwd, bwd):
+        _lib.require_gpu_tensor(f, "morph_frames flow")
+        if f.dtype != torch.float32 or tuple(f.shape) != (h, w, 2):
+            raise NstError(f"morph_frames: flows must be float32 [{h},{w},2], got {f.dtype} {tuple(f.shape)}")
+    fwd, bwd = fwd.contiguous(), bwd.contiguous()
+    k = len(t)
+    step = _lib.NST_MORPH_MAX_FRAMES if not batch else max(1, min(int(batch), _lib.NST_MORPH_MAX_FRAMES))
+    rows = kernel_schedule(np.asarray(t, np.float64), np.asarray(alpha, np.float64))
+    out = torch.empty((k, h, w, 3), dtype=torch.uint8, device=a.device)
+    pf = ctypes.POINTER(ctypes.c_float)
+    for s in range(0, k, step):
+        e = min(k, s + step)
+        r = [np.ascontiguousarray(x[s:e]) for x in rows]
+        check(lib().nst_morph_frames(a.data_ptr(), b.data_ptr(), fwd.data_ptr(), bwd.data_ptr(), h, w, e - s,
+                                     *[x.ctypes.data_as(pf) for x in r], out[s:e].data_ptr(),
+                                     _lib.stream_ptr(a.device)), "nst_morph_frames")
+    return out
+
+
+def morph_flows(img1_u8: torch.Tensor, img2_u8: torch.Tensor, preset: str = "v2") -> Tuple[torch.Tensor, torch.Tensor]:
+    """(forward, backward) flows [h,w,2] of a transition, post-processed as the preset says."""
+    if preset not in PRESETS:
+        raise ValueError(f"preset must be one of {sorted(PRESETS)}, got {preset!r}")
+    p = PRESETS[preset]
+    a, b = _u8(img1_u8, "optical_flow_morph img1", 3), _u8(img2_u8, "optical_flow_morph img2", 3)
+    if a.shape != b.shape or a.shape[2] != 3:
+        raise NstError(f"optical_flow_morph: images must both be [h,w,3], got {tuple(a.shape)} and {tuple(b.shape)}")
+    g = gray_cv_u8(torch.stack([a, b]))
+    if p["pre_blur"]:
+        g = gauss_u8(g)
+    flows = farneback_ex(g, g.flip(0), p["farneback"], _lib.NST_FLOW_GAUSSIAN)  # (g1, g2) and (g2, g1)
+    if p["post"]:
+        flows = flow_post(flows, (1.0, -1.0))
+    return flows[0], flows[1]
+
+
+def optical_flow_morph(img1_u8: torch.Tensor, img2_u8: torch.Tensor, num_interp_frames: int = 72, preset: str = "v2",
+                       easing: str = "smooth", batch: Optional[int] = None) -> torch.Tensor:
+    """RGB uint8 [h,w,3] device tensors -> the transition's frames, uint8 [k,h,w,3]."""
+    t, alpha = schedule(int(num_interp_frames), preset, easing)
+    fwd, bwd = morph_flows(img1_u8, img2_u8, preset)
+    return morph_frames(img1_u8, img2_u8, fwd, bwd, t, alpha, batch)
+
+
+# ---- CLI ----
+def cover_geometry(w: int, h: int, tw: int, th: int) -> Tuple[int, int, int, int]:
+    """morph_v2.py:704-712: (new_w, new_h, start_x, start_y) of cover + centre crop.  int(w * scale) can fall one
+    short of the target through the float product; the size is then the target (the reference would crop short)."""
+    scale = max(tw / w, th / h)
+    nw, nh = max(int(w * scale), tw), max(int(h * scale), th)
+    return nw, nh, (nw - tw) // 2, (nh - th) // 2
+
+
+def list_images(images_dir: Optional[str], images: Optional[Sequence[str]]) -> List[Path]:
+    """--images in the order given; --images_dir: every *.jpg, *.jpeg, *.png, sorted by path (the slideshow's rule)."""
+    if images:
+        return [Path(p) for p in images]
+    files: List[Path] = []
+    for pat in IMAGE_PATTERNS:
+        files.extend(Path(images_dir).glob(pat))
+    return sorted(files, key=str)
+
+
+def total_frames(n_images: int, k: int, hold_frames: int, hold_end: int) -> int:
+    return n_images * hold_frames + (n_images - 1) * k + hold_end
+
+
+def parse_size(s: str) -> Tuple[int, int]:
+    try:
+        w, h = (int(v) for v in s.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"size must be WxH, got {s!r}")
+    if w < 2 or h < 2:
+        raise argparse.ArgumentTypeError(f"size must be at least 2x2, got {s!r}")
+    return w, h
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m neuralstyletransferv1_amd.morph",
+                                 description="Optical-flow morph slideshow between stills on the GPU")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--images_dir", type=str, help="directory of stills (*.jpg, *.jpeg, *.png, sorted)")
+    src.add_argument("--images", type=str, nargs="+", help="stills in slideshow order")
+    ap.add_argument("--size", type=parse_size, default=(1920, 1080), help="output WxH")
+    ap.add_argument("--fps", type=float, default=24.0)
+    ap.add_argument("--morph_seconds", type=float, default=2.0, help="frames per transition = int(fps * seconds)")
+    ap.add_argument("--preset", choices=sorted(PRESETS), default="v2")
+    ap.add_argument("--easing", choices=EASINGS, default="smooth", help="warp timing of preset v2")
+    ap.add_argument("--hold_frames", type=int, default=0, help="frames each still is shown before its transition")
+    ap.add_argument("--hold_end", type=int, default=24, help="extra frames of the last still")
+    ap.add_argument("--output_dir", type=str, required=True)
+    ap.add_argument("--output_prefix", type=str, default="morph_frame")
+    ap.add_argument("--image_ext", choices=["png", "jpg"], default="png")
+    ap.add_argument("--jpeg_quality", type=int, default=85)
+    ap.add_argument("--png_writer", choices=["fast", "pil", "gpu"], default="pil")
+    ap.add_argument("--jpeg_writer", choices=["pil", "gpu"], default="pil")
+    ap.add_argument("--output_video", type=str, default=None, help="also assemble the frames with ffmpeg")
+    ap.add_argument("--batch", type=int, default=24, help="frames per nst_morph_frames launch (and per write)")
+    ap.add_argument("--device", type=str, default="cuda:0")
+    return ap
+
+
+def load_fitted(path: Path, tw: int, th: int, device: torch.device) -> torch.Tensor:
+    """Pillow decode -> RGB -> cover (GPU LANCZOS) -> centre crop: uint8 [th,tw,3] on the device."""
+    from PIL import Image
+
+    from .deeplab import Resampler
+    with Image.open(path) as im:
+        rgb = np.array(im.convert("RGB"), dtype=np.uint8)
+    h, w = rgb.shape[:2]
+    nw, nh, sx, sy = cover_geometry(w, h, tw, th)
+    x = torch.from_numpy(rgb).to(device)[None]
+    if (nw, nh) != (w, h):
+        x = Resampler("lanczos", h, w, nh, nw, device)(x)
+    return x[0, sy:sy + th, sx:sx + tw].contiguous()
+
+
+class FrameWriter:
+    """Numbered files {prefix}_{0001..}.{ext} through the frame loop's writers."""
+
+    def __init__(self, out_dir: Path, prefix: str, ext: str, quality: int, png_writer: str, jpeg_writer: str):
+        self.dir, self.prefix, self.ext, self.quality = out_dir, prefix, ext, int(quality)
+        self.png_writer, self.jpeg_writer = png_writer, jpeg_writer
+        self.count = 0
+
+    def write(self, frames_u8: torch.Tensor) -> None:
+        from PIL import Image
+        blobs = None
+        if self.ext == "jpg" and self.jpeg_writer == "gpu":
+            from .jpegio import jpeg_bytes_gpu
+            blobs = jpeg_bytes_gpu(frames_u8, self.quality)
+        elif self.ext == "png" and self.png_writer == "gpu":
+            from .pngio import png_bytes_gpu
+            blobs = png_bytes_gpu(frames_u8)
+        host = None if blobs is not None else frames_u8.cpu().numpy()
+        for j in range(frames_u8.shape[0]):
+            self.count += 1
+            path = self.dir / f"{self.prefix}_{self.count:04d}.{self.ext}"
+            if blobs is not None:
+                path.write_bytes(blobs[j])
+            elif self.ext == "jpg":
+                Image.fromarray(host[j]).save(path, format="JPEG", quality=self.quality)
+            elif self.png_writer == "fast":
+                from .pngio import write_png
+                write_png(path, host[j])
+            else:
+                Image.fromarray(host[j]).save(path)
+
+
+def _hold(wr: FrameWriter, img: torch.Tensor, n: int, step: int) -> None:
+    for s in range(0, n, step):
+        wr.write(img[None].repeat(min(step, n - s), 1, 1, 1))
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    args = build_parser().parse_args(argv)
+    files = list_images(args.images_dir, args.images)
+    if len(files) < 2:
+        print(f"[morph] need at least 2 images, got {len(files)}", file=sys.stderr)
+        return 2
+    k = int(args.fps * args.morph_seconds)
+    if k < 1 or args.hold_frames < 0 or args.hold_end < 0 or args.batch < 1:
+        print("[morph] need int(fps * morph_seconds) >= 1, hold counts >= 0 and --batch >= 1", file=sys.stderr)
+        return 2
+    device = torch.device(args.device)
+    tw, th = args.size
+    out_dir = Path(args.output_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    wr = FrameWriter(out_dir, args.output_prefix, args.image_ext, args.jpeg_quality, args.png_writer, args.jpeg_writer)
+    t, alpha = schedule(k, args.preset, args.easing)
+    step = max(1, min(args.batch, _lib.NST_MORPH_MAX_FRAMES))
+    cur = load_fitted(files[0], tw, th, device)
+    for idx in range(len(files)):
+        _hold(wr, cur, args.hold_frames, step)
+        if idx + 1 < len(files):
+            nxt = load_fitted(files[idx + 1], tw, th, device)
+            fwd, bwd = morph_flows(cur, nxt, args.preset)
+            for s in range(0, k, step):
+                wr.write(morph_frames(cur, nxt, fwd, bwd, t[s:s + step], alpha[s:s + step]))
+            cur = nxt
+        print(f"[morph] {idx + 1}/{len(files)} {files[idx].name}: {wr.count} frames")
+    _hold(wr, cur, args.hold_end, step)
+    assert wr.count == total_frames(len(files), k, args.hold_frames, args.hold_end)
+    if args.output_video:
+        from .pipeline import assemble_video
+        assemble_video(out_dir, Path(args.output_video), args.fps, None, args.output_prefix)
+    print(f"[morph] wrote {wr.count} frames to {out_dir}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
