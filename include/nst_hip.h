@@ -124,7 +124,7 @@ int nst_create(int arch, const nst_param* params, int n_params, int compute_dtyp
  * generic ones on the same model.  NST_KSEL_UNFUSED_RESIDUAL runs the residual add as its own
  * kernel instead of fusing it into the next conv's fill.  Unknown bits -> NST_E_INVALID.
  */
-#define NST_KSEL_NO_WSTAT 0x1             /* residual-trunk weight-stationary conv (conv_wstat.hip) */
+#define NST_KSEL_NO_WSTAT 0x1             /* residual-trunk weight-stationary conv (conv_wst16.hip) */
 #define NST_KSEL_NO_WPHASE 0x2            /* x2 up-conv phase kernel (conv_wphase.hip) */
 #define NST_KSEL_NO_WS2 0x4               /* stride-2 down-conv kernel (conv_ws2.hip) */
 #define NST_KSEL_NO_WS9 0x8               /* 9x9 first-layer kernel (conv_ws9.hip) */
@@ -207,7 +207,7 @@ typedef struct nst_op_desc {
   int conv_h, conv_w; /* conv output extent (before the NST centre crop) */
   int out_h, out_w; /* stored output extent */
   int cin_stride, cout_stride;
-  int kernel_mode;  /* internal kernel family (0 generic, 1 phase, 2 x-shift, 3 out9, 4 wstat, 5 wphase, 6 ws2, 7 ws9) */
+  int kernel_mode;  /* internal kernel family (0 generic, 1 phase, 2 x-shift, 3 out9, 4 wstat = the weight-stationary trunk kernel, 5 wphase, 6 ws2, 7 ws9) */
   int elem_bytes;   /* bytes per element of what the op writes (act[i]): 2 (bf16 / fp16) or 4 (fp32) */
   int in_elem_bytes;  /* bytes per element of src (NST_BUF_INPUT: the staged first-layer operand, 2 or 4) */
   int res_elem_bytes; /* bytes per element of the joined residual stream (res_buf / res_out), 0 if none */

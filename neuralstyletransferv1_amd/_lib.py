@@ -106,7 +106,7 @@ class NstError(RuntimeError):
 TRUNK_KERNEL_SOURCES = ("csrc/conv_wst16.hip", "csrc/conv_ws_common.h", "csrc/conv_impl.h")
 
 
-def kernel_sha(sources=TRUNK_KERNEL_SOURCES, obj: str = "conv_wstat") -> str:
+def kernel_sha(sources, obj: str) -> str:
     """sha256[:16] of a kernel's sources and the build flags of its translation unit `obj` (the key of its PMC
     summary under profiles/)."""
     import hashlib

@@ -3,7 +3,8 @@
 // Replaces UpsampleConvLayer (transformer_net.py:79-99: nearest x2 + ReflectionPad(1) + 3x3) and
 // ConvTranspose2d(3, s2, p1, op1) (transformer_net_nst.py:46-59) for the 128->64 and 64->32
 // layers, with the producer's InstanceNorm + ReLU (or the last residual join) in the fill and this
-// layer's InstanceNorm partial sums in the epilogue — the conv_wstat.hip machinery applied to the
+// layer's InstanceNorm partial sums in the epilogue — the weight-stationary machinery of the residual-trunk kernel
+// (weights resident in registers, LDS-DMA halo staging under counted vmcnt waits, a persistent tile walk) applied to the
 // phase decomposition of conv_impl.h's MODE_PHASE: output pixel (2y + a, 2x + b) is a 2x2 conv
 // over the SOURCE grid with phase-summed weights.
 //
@@ -13,8 +14,10 @@
 //     2 x odd chunks, conflict-free ds_read_b128); halo row y of x-tap tx is the B operand of rows
 //     y - ty for both y-taps, so each read feeds two MFMAs per 16-channel subtile.
 //   * K order part-major (part q = input channels 32q..32q+31 = one K step per tap); the next tile's
-//     halo streams in by LDS-DMA into a 4-slot staging ring (conv_wstat.hip's schedule, generalised
-//     to 2, 3 or 4 parts) and is consumed (IN + ReLU / residual join) into each region once freed.
+//     halo streams in by LDS-DMA into a 4-slot staging ring, one half part (unit) per slot: unit u lands in slot
+//     u % 4, and unit u + 4 (two parts ahead, wrapping into the next tile) is requested as soon as unit u has been
+//     consumed (IN + ReLU / residual join) into its halo region, which the K loop has freed by then.  The same
+//     schedule serves 2, 3 or 4 parts (three parts: six slots, one per unit).
 //   * one InstanceNorm partial row per phase and tile (part_rows = 4).
 #include <algorithm>
 #include <cstring>
@@ -25,7 +28,7 @@ namespace nst {
 
 constexpr int WP_RING = 3;  // operand reads in flight ahead of the MFMAs
 // the conv bias as the C operand of each (row, subtile)'s first MFMA and the epilogue's InstanceNorm sums as packed
-// f32 pairs (after the MFMA drain): conv_wstat.hip's epilogue, for the phase kernels whose epilogue is half their VALU
+// f32 pairs (after the MFMA drain): a short epilogue for the phase kernels, where it is half their VALU work
 #ifndef NST_WP_BIAS_C
 #define NST_WP_BIAS_C 1
 #endif
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(512) void wphase_kernel(ConvParams p) {
   }
   if (tid < COUT) ((float*)(smem + C::BIAS_OFF))[tid] = p.bias[tid];
 
-  // ---- halo staging (conv_wstat.hip) ----
+  // ---- halo staging: LDS-DMA requests into the slot ring, issued four units (two parts) ahead of their consume ----
   // one buffer resource per tensor for the whole launch (the launcher keeps a launch's frames below
   // 2^31 bytes): a frame is a 32-bit offset, no 64-bit scalar math per request
   const uint32_t fb = (uint32_t)p.hs * p.ws * p.cs * 2;
@@ -245,8 +248,10 @@ __global__ __launch_bounds__(512) void wphase_kernel(ConvParams p) {
   };
   auto consume = [&](const Work& wk, int u, const Item& it) { consume_s(wk, u, u % C::NSLOT, it); };
   auto consume_p = [&](const Work& wk, int pp, const Item& it) { consume_s(wk, 2 * pp + phalf, pp % 2, it); };
-  // vmcnt accounting as in conv_wstat.hip: 3 units' requests after unit g's, plus the epilogue's
-  // TH * NS output stores and NS partial stores when one lies in between
+  // vmcnt accounting: a wave's vector-memory operations (LDS-DMA loads, output and partial stores) retire in issue
+  // order, so unit g's data has landed once at most the operations issued after its request are outstanding.  Counted:
+  // the 3 later units' requests (DPU loads each), plus the epilogue's TH * NS output stores (NST with the LDS
+  // output tile) and NS partial stores when an epilogue lies in between
   constexpr int DPU = RES ? 2 : 1;
   // paired: one part's requests (DPU) after the consumed part's, two parts in flight
   constexpr int KIN = (PR ? 1 : 3) * DPU;
@@ -386,7 +391,10 @@ __global__ __launch_bounds__(512) void wphase_kernel(ConvParams p) {
     }
   };
 
-  // ---- persistent walk (conv_wstat.hip's, with NPART parts) ----
+  // ---- persistent walk: workgroup b runs work items w0, w0 + G, ... (frame-major, then row-major tiles).  XCD-aware
+  // start (w0 above): workgroups are dealt to the 8 XCDs round-robin, so with G % 8 == 0 the G / 8 workgroups sharing
+  // XCD b % 8 take consecutive items and neighbouring tiles' halos meet in that XCD's L2.  Each iteration's K loop
+  // stages the next tile under the current tile's MFMAs ----
   Work cur = decode(w0);
   int wn = w0 + G;
   const int last = p.n_work - 1;

@@ -4,7 +4,7 @@
 // Replaces ConvLayer(128, 128, 3, 1) of the first two residual blocks (transformer_net.py:57-76 res1, res2;
 // transformer_net_nst.py:28-43) in the split-precision head: fp32 activations in HBM, each staged operand value v
 // kept as the fp16 pair xh = RNE(v), xl = RNE(v - xh) (two planes of the LDS entry), the weights fp16 in registers
-// (128 x 1152 = 144 VGPRs per wave, as conv_wstat.hip), and two MFMAs per K step, Wh xh and Wh xl, accumulated
+// (128 x 1152 over 8 waves = 144 VGPRs per wave), and two MFMAs per K step, Wh xh and Wh xl, accumulated
 // in one chain: the operand keeps ~22 bits (its rounding is what reaches the frame most, tests/precision_study.py:
 // "o" and "s" of these layers; their fp16 weights add little).  Fill: the producer's InstanceNorm + ReLU in fp32
 // (or the residual stream as stored: RAW), the layer's InstanceNorm partial sums in the epilogue, fp32 output.

@@ -78,7 +78,7 @@ enum AxisMode { AX_REFLECT = 0, AX_REFLECT_UP2 = 1, AX_ZERO = 2, AX_ZERO_PREREFL
 
 // conv_kernel mappings (see conv_impl.h)
 enum ConvMode { MODE_STD = 0, MODE_PHASE = 1, MODE_XSHIFT = 2, MODE_KYROT = 3, MODE_WSTAT = 4, MODE_WPHASE = 5, MODE_WS2 = 6, MODE_WS9 = 7,
-                MODE_WS1S = 8 };  // WS1S: conv_ws1s.hip (split-operand stride-1 trunk conv)  // KYROT: conv_out9.hip, WSTAT: conv_wstat.hip, WPHASE: conv_wphase.hip, WS2: conv_ws2.hip, WS9: conv_ws9.hip
+                MODE_WS1S = 8 };  // WS1S: conv_ws1s.hip (split-operand stride-1 trunk conv)  // KYROT: conv_out9.hip, WSTAT: the weight-stationary residual-trunk kernel (conv_wst16.hip), WPHASE: conv_wphase.hip, WS2: conv_ws2.hip, WS9: conv_ws9.hip
 
 struct ConvParams {
   // input

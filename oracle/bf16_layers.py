@@ -121,7 +121,7 @@ def fill_operand(y: torch.Tensor, ys: Optional[torch.Tensor], in_relu: bool, r: 
     No residual: fma(y, scale, shift) rounded once to fp32 (then bf16), ReLU.  Residual join
     (ResidualBlock): r' + (y*scale + shift) in unfused fp32, r' = relu(r*scale_r + shift_r) if rs
     (bf16: r' = the normalised fill of r, rounded to bf16 — block 1's input x_0 as the trunk stores
-    it, conv_wstat.hip XO)."""
+    it, conv_wst16.hip XO)."""
     rnd = (lambda t: rnd16(t, fmt)) if round_bf16 else (lambda t: t)
     if r is None:
         if ys is None:

@@ -2,8 +2,8 @@
 
 Every op of the program is recomputed on the CPU from the engine's own stored input (captured by
 nst_forward_capture) with the bf16 mode's rounding points (oracle/bf16_layers.py), so each kernel
-is checked alone: conv_ws9 (first layer), conv_ws2 (down-convs), conv_wstat (residual trunk, plain
-and with the fused residual join), conv_wphase (x2 up-convs), conv_out9 (output conv + decode +
+is checked alone: conv_ws9 (first layer), conv_ws2 (down-convs), conv_wst16 (residual trunk, plain
+and with the fused residual join: 16x16x32 MFMAs, one wave per SIMD, 8x32 tiles), conv_wphase (x2 up-convs), conv_out9 (output conv + decode +
 truncation), and on ReCoNet (InstanceNorm and FRN/TLU) the generic bf16 kernels.  Bars (tests/layer_check.py): stored bf16
 outputs within 1 bf16 ulp (or 4e-6 of the layer's max |value| where the sum cancels), <= 0.1 % of
 elements 1 ulp off (measured <= 0.03 %), IN statistics within 1e-5, joined residual streams bit-exact, raw fp32 output

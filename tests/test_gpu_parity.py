@@ -442,8 +442,8 @@ def test_prepadded_image_layer_bit_exact(arch):
     ("johnson", 1080, 1920),  # the bench shape (270x480 trunk), one frame
 ])
 def test_weight_stationary_trunk_vs_generic(arch, h, w):
-    """The weight-stationary residual-trunk conv (conv_wstat.hip: 32x32x16 MFMAs, bias-initialised
-    accumulators, its own K order) against the generic persistent kernel on the same bf16 model:
+    """The weight-stationary residual-trunk conv (conv_wst16.hip: 16x16x32 MFMAs, one wave per SIMD, 8x32 tiles,
+    its own K order) against the generic persistent kernel on the same bf16 model:
     every trunk layer's bf16 rounding may land differently, so the bar is the bf16 mode's own
     (SSIM vs each other well above the 0.98 oracle bar, few-LSB frames, raw outputs close)."""
     frames = torch.from_numpy(synthetic.make_frames(2 if h < 512 else 1, h, w, seed=21)).cuda()
@@ -468,6 +468,27 @@ def test_weight_stationary_trunk_batch_chunks():
     a = net.stylize_frames(frames, "imagenet_255")
     for i in (0, 15, 16, 19):
         assert torch.equal(net.stylize_frames(frames[i:i + 1].contiguous(), "imagenet_255")[0], a[i]), i
+
+
+@pytest.mark.parametrize("ksel", [(), ("unfused_residual",)], ids=["default", "unfused_residual"])
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("arch", ["johnson", "nst"])
+def test_weight_stationary_trunk_is_selected(arch, dtype, ksel):
+    """Kernel selection of the residual trunk: conv_wst16.hip's table is the only one with weight-stationary
+    entries for the 3x3 128 -> 128 convs, so a selection slip would land on the generic kernel, which passes every
+    parity bar at about half the speed.  By default all ten trunk convs of the program report kernel_mode 4
+    (MODE_WSTAT); with no_wstat none does.  Reads the handle's program only: no forward pass."""
+    dev = torch.device("cuda", 0)
+
+    def trunk_modes(sel):
+        eng = _net(arch, 6, dtype, sel).engine(dev)
+        names = eng.layer_names()
+        convs = [d for d in eng.op_descs(2, 70, 90) if d["kind"] == 0 and names[d["layer"]].startswith("res")]
+        assert len(convs) == 10 and all(d["cin_stride"] == 128 and d["cout_stride"] == 128 for d in convs)
+        return [d["kernel_mode"] for d in convs]
+
+    assert trunk_modes(ksel) == [4] * 10
+    assert 4 not in trunk_modes(ksel + ("no_wstat",))
 
 
 @pytest.mark.parametrize("arch,h,w", [

@@ -1,5 +1,5 @@
 """Build report: scratch use by the kernels whose LDS-DMA loads are waited for with hand-counted
-`s_waitcnt vmcnt(N)` (conv_wstat, conv_wphase, conv_ws9, conv_gemm's LDS-DMA kernel) and the other asm-MFMA kernel
+`s_waitcnt vmcnt(N)` (conv_wst16, conv_wphase, conv_ws9, conv_gemm's LDS-DMA kernel) and the other asm-MFMA kernel
 (conv_ws2).  Those kernels are meant to
 keep everything in registers with their K loops fully unrolled; scratch means spills or a loop the compiler kept
 rolled with its accumulators in memory (the Makefile's per-file unroll flag missing: a deconv1 variant ran 6x

@@ -19,8 +19,8 @@ _TARG = {"DF16b": "bf16", "DF16_": "fp16", "f": "float"}
 
 
 def pretty(k):
-    """hipcc leaves the _Float16/__bf16 template kernels mangled in the trace: _ZN3nst12wstat_kernelIDF16bLi8ELi0ELb0ELb0EE...
-    -> 'nst::wstat_kernel<bf16, 8, 0, false, false>'"""
+    """hipcc leaves the _Float16/__bf16 template kernels mangled in the trace: _ZN3nst12wst16_kernelIDF16bLi8ELi0ELb0ELb0EE...
+    -> 'nst::wst16_kernel<bf16, 8, 0, false, false>'"""
     m = re.match(r"_ZN3nst(\d+)(\w+?)I((?:DF16b|DF16_|f|Li-?\d+E|Lb[01]E)+)EEvNS_10ConvParamsE", k)
     if not m or len(m.group(2)) != int(m.group(1)):
         return k
