@@ -603,6 +603,69 @@ int nst_morph_frames(const uint8_t* img1, const uint8_t* img2, const float* flow
                      int w, int k, const float* t, const float* one_minus_t, const float* wa, const float* wb,
                      uint8_t* out, void* stream);
 
+/* ---- Camera stage of the morph slideshow (scripts/morph_v2.py:624-999, create_morph_video with --pan_zoom; camera.py):
+ * what the reference does to every morph frame before the video writer.  cv2 absent: every restatement below is
+ * parity unpinned; tests/camera_ref.py is the numpy yardstick and the kernels equal it byte for byte (integer fixed
+ * point, fp32 without contraction, or double).  Every entry point is batched over n <= NST_CAMERA_MAX_FRAMES frames
+ * [n,h,w,3] u8 RGB (device) with per-frame parameters in host arrays, checks its arguments before any launch
+ * (NST_E_INVALID; frame sizes outside 1..32768 NST_E_SHAPE) and launches on `stream`; out != in. ---- */
+#define NST_CAMERA_MAX_FRAMES 32
+#define NST_CAMERA_MAX_SMOOTH 15
+/* (a) zoom pulse: cv2.resize(frame, (nw[i], nh[i]), INTER_LINEAR) cropped back to w x h at ((nw-w)/2, (nh-h)/2);
+ * nw >= w, nh >= h.  8-bit linear path: scale = w/nw in double, fx = (float)((dx+0.5)*scale - 0.5), sx = floor(fx),
+ * fx -= sx, sx < 0 -> (0, 0), sx >= w-1 -> (w-1, 0); taps (short)rint((1-fx)*2048), (short)rint(fx*2048); rows
+ * likewise without the reset, rows sy and sy+1 clipped to the frame; S = S[sx]*a0 + S[sx+1]*a1,
+ * out = (((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2. */
+int nst_camera_pulse_u8(const uint8_t* in, int n, int h, int w, const int* nw, const int* nh, uint8_t* out,
+                        void* stream);
+/* (b) cv2.getRectSubPix(frame, (pw, ph), (cx[i], cy[i])), u8 -> u8 [n,ph,pw,3]: c -= (p-1)*0.5f, ip = floor(c),
+ * a = cx-ip.x, b = cy-ip.y in fp32; weights rint(v*65536) of (1-a)(1-b), a(1-b), (1-a)b, ab, 1-b, b; pixel =
+ * (a11*s0[j] + a12*s0[j+1] + a21*s1[j] + a22*s1[j+1] + 32768) >> 16; a row whose lower tap is past h-1 uses
+ * s1 = s0, a column whose right tap is past w-1 reads column w-1 alone, (b1*s0 + b2*s1 + 32768) >> 16.  Only
+ * ip >= 0 and ip + patch <= size is built (all the camera produces); anything else NST_E_INVALID. */
+int nst_camera_rect_subpix_u8(const uint8_t* in, int n, int h, int w, int pw, int ph, const float* cx, const float* cy,
+                              uint8_t* out, void* stream);
+/* (c) cv2.resize(crop, (tw, th), INTER_LANCZOS4) -> [n,th,tw,3]; frame i's crop is the top-left ch[i] x cw[i] region
+ * of its h x w buffer.  Table driven: device arrays xofs int32 [n,tw] (floor(fx), never reset), xcoef int16 [n,tw,8]
+ * (saturate_cast<short>(rint(c*2048)) of interpolateLanczos4(fx)), yofs [n,th], ycoef [n,th,8]; frame i reads slot i.
+ * Taps at ofs-3 .. ofs+4, each index clamped to the crop in the kernel (no table content reads outside it); rows
+ * summed in int32, columns in int64, out = sat_u8((v + (1<<21)) >> 22). */
+int nst_camera_lanczos_u8(const uint8_t* in, int n, int h, int w, const int* cw, const int* ch, int tw, int th,
+                          const int32_t* xofs, const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef,
+                          uint8_t* out, void* stream);
+/* (d) apply_hue_shift (morph_v2.py:324-345) where hue_on[i], a copy otherwise (the caller applies |shift| < 0.1):
+ * cv2's 8-bit BGR2HSV (sdiv / hdiv tables in 12 bits), h = np.remainder(float32(h) + hue_half[i], 180) in fp32
+ * truncated to u8 (hue_half = float32(shift / 2)), HSV2BGR's float path, sat_u8(rint(x*255.f)).  in == out allowed. */
+int nst_camera_hue_u8(const uint8_t* in, int n, int h, int w, const int* hue_on, const float* hue_half, uint8_t* out,
+                      void* stream);
+/* (e) temporal_smooth_frames (morph_v2.py:282-321) with NumPy >= 2 promotion: window = frames first .. first+win_n-1
+ * of a sequence of seq_len frames, out = smoothed frames out_first .. out_first+out_count-1.  Per byte: acc (fp32)
+ * = (float)((double)acc + (double)pixel * weights[j]) over the taps idx = g + j - kernel_size/2 inside the sequence,
+ * total = the double sum of their weights in tap order, out = (u8)((double)acc / total) truncated.  weights:
+ * kernel_size host doubles (1 <= kernel_size <= NST_CAMERA_MAX_SMOOTH).  A valid tap outside the window ->
+ * NST_E_INVALID.  seq_len <= kernel_size: the frames are copied unchanged (the call site's condition). */
+int nst_camera_smooth_u8(const uint8_t* window, int win_n, int h, int w, int first, int seq_len, int out_first,
+                         int out_count, int kernel_size, const double* weights, uint8_t* out, void* stream);
+/* (f) the fused stage: frame i goes through pulse (pulse_w x pulse_h; (w, h) = none), then getRectSubPix of
+ * (patch_w, patch_h) at (cx, cy), then, zoom != 0, Lanczos to tw x th with table slot `table` (< table_slots), or,
+ * zoom == 0, nothing (patch = target); then the hue rotation where hue_on.  The u8 rounding between the stages is
+ * kept: taps of an earlier stage are recomputed, not skipped.  Pan-phase frames are one gather pass over the input
+ * frame and one store; zoom-phase patches go through `scratch` (nst_camera_scratch_bytes; smaller NST_E_WORKSPACE).
+ * out u8 [n,th,tw,3]; tw <= w, th <= h (NST_E_SHAPE).  At most two launches. */
+typedef struct nst_camera_frame {
+  int pulse_w, pulse_h;
+  int zoom;
+  int patch_w, patch_h;
+  float cx, cy;
+  int hue_on;
+  float hue_half;
+  int table;
+} nst_camera_frame;
+int nst_camera_scratch_bytes(const nst_camera_frame* frames, int n, size_t* out);
+int nst_camera_frames_u8(const uint8_t* in, int n, int h, int w, const nst_camera_frame* frames, int tw, int th,
+                         const int32_t* xofs, const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef,
+                         int table_slots, uint8_t* out, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- PNG encode on the owner rank (pipeline.py:2099-2119 `Image.fromarray(out).save(path)`, the reference's
  * default --image_ext png at :2170) ----
  * n u8 frames [n,h,w,c] (c = 1 grey, 3 RGB, 4 RGBA; device) -> n complete PNG files, file j at out + j*out_stride,

@@ -59,9 +59,12 @@ EXPORTED_SYMBOLS = (
     "nst_jpeg_enc_bound", "nst_jpeg_enc_workspace_bytes", "nst_jpeg_encode_u8",
     "nst_flow_scratch_floats_ex", "nst_flow_farneback_ex", "nst_gray_cv_u8", "nst_gauss_u8", "nst_morph_flow_post",
     "nst_morph_frames",
+    "nst_camera_pulse_u8", "nst_camera_rect_subpix_u8", "nst_camera_lanczos_u8", "nst_camera_hue_u8",
+    "nst_camera_smooth_u8", "nst_camera_scratch_bytes", "nst_camera_frames_u8",
 )
 NST_FLOW_GAUSSIAN = 256  # cv2.OPTFLOW_FARNEBACK_GAUSSIAN (nst_flow_farneback_ex flags)
 NST_MORPH_MAX_FRAMES = 128  # frames per nst_morph_frames launch
+NST_CAMERA_MAX_FRAMES, NST_CAMERA_MAX_SMOOTH = 32, 15  # frames per nst_camera_* call, widest temporal kernel
 NST_E_INVALID, NST_E_SHAPE, NST_E_WORKSPACE, NST_E_DATA = -1, -3, -5, -7
 NST_JPEG_444, NST_JPEG_422, NST_JPEG_420 = 0, 1, 2
 # region compositor limits / geometry kinds (include/nst_hip.h NST_REGION_*, NST_RG_*)
@@ -90,6 +93,13 @@ class NstOpDesc(ctypes.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class NstCameraFrame(ctypes.Structure):
+    """nst_camera_frame: one frame's camera work (include/nst_hip.h "Camera stage")."""
+    _fields_ = [("pulse_w", ctypes.c_int), ("pulse_h", ctypes.c_int), ("zoom", ctypes.c_int),
+                ("patch_w", ctypes.c_int), ("patch_h", ctypes.c_int), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("hue_on", ctypes.c_int), ("hue_half", ctypes.c_float), ("table", ctypes.c_int)]
 
 
 _lib = None
@@ -257,6 +267,17 @@ def lib() -> ctypes.CDLL:
         L.nst_morph_frames.argtypes = [vp, vp, vp, vp, i, i, i, pf, pf, pf, pf, vp, vp]
         for name in ("nst_flow_scratch_floats_ex", "nst_flow_farneback_ex", "nst_gray_cv_u8", "nst_gauss_u8",
                      "nst_morph_flow_post", "nst_morph_frames"):
+            getattr(L, name).restype = i
+        pcf = ctypes.POINTER(NstCameraFrame)
+        L.nst_camera_pulse_u8.argtypes = [vp, i, i, i, pi, pi, vp, vp]
+        L.nst_camera_rect_subpix_u8.argtypes = [vp, i, i, i, i, i, pf, pf, vp, vp]
+        L.nst_camera_lanczos_u8.argtypes = [vp, i, i, i, pi, pi, i, i, vp, vp, vp, vp, vp, vp]
+        L.nst_camera_hue_u8.argtypes = [vp, i, i, i, pi, pf, vp, vp]
+        L.nst_camera_smooth_u8.argtypes = [vp, i, i, i, i, i, i, i, i, pd, vp, vp]
+        L.nst_camera_scratch_bytes.argtypes = [pcf, i, psz]
+        L.nst_camera_frames_u8.argtypes = [vp, i, i, i, pcf, i, i, vp, vp, vp, vp, i, vp, vp, sz, vp]
+        for name in ("nst_camera_pulse_u8", "nst_camera_rect_subpix_u8", "nst_camera_lanczos_u8", "nst_camera_hue_u8",
+                     "nst_camera_smooth_u8", "nst_camera_scratch_bytes", "nst_camera_frames_u8"):
             getattr(L, name).restype = i
         for name in ("nst_png_bound", "nst_png_workspace_bytes", "nst_png_encode_u8"):
             getattr(L, name).restype = i

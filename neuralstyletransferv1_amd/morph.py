@@ -25,9 +25,16 @@ reference's cv2.INTER_LANCZOS4 (an 8-tap kernel without Pillow's support scaling
 reference's.  cv2 is not installed in this environment, so the grey, blur, Farneback, remap and addWeighted
 restatements are parity unpinned; tests/morph_ref.py is their numpy yardstick.
 
-Out of scope (not built): morph_v2's Ken Burns pan / zoom, zoom pulse, hue rotation and temporal_smooth_frames (its
-float promotion depends on the numpy version, and it truncates), its DeepLab and Magenta orchestration, and
-morph_faces.py's face detection.
+With --pan_zoom > 1 the CLI is create_morph_video's Ken Burns path (morph_v2.py:839-948): the stills load at pan
+size (camera.load_for_pan), the morph runs at that size, and every output frame -- held frames included -- goes
+through the camera stage of camera.py on the device (zoom pulse, zoom-in phase, sub-pixel pan, hue rotation) by its
+global index g, progress = g / max(1, total - 1); temporal_smooth_frames then runs over the whole sequence, streamed
+with kernel_size // 2 frames of halo between batches.  With --hold_frames 0 the frame count and the progress are the
+reference's.  Without --pan_zoom nothing changes, and the camera flags are refused (the reference silently ignores
+them).
+
+Out of scope (not built): morph_v2's DeepLab and Magenta orchestration, its crossfade fallback after a failed morph,
+cv2's video writer, and morph_faces.py's face detection.
 """
 from __future__ import annotations
 
@@ -50,6 +57,7 @@ PRESETS = {
 }
 EASINGS = ("linear", "smooth", "smoother")
 IMAGE_PATTERNS = ("*.jpg", "*.jpeg", "*.png")
+PAN_DIRECTIONS = ("horizontal", "vertical", "diagonal", "diagonal_reverse")
 
 
 def ease_in_out_cubic(t: float) -> float:
@@ -253,7 +261,57 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--output_video", type=str, default=None, help="also assemble the frames with ffmpeg")
     ap.add_argument("--batch", type=int, default=24, help="frames per nst_morph_frames launch (and per write)")
     ap.add_argument("--device", type=str, default="cuda:0")
+    cam = ap.add_argument_group("camera (morph_v2's Ken Burns path; all of it needs --pan_zoom > 1)")
+    cam.add_argument("--pan_zoom", type=float, default=None, help="morph at pan_zoom x the output size and pan across")
+    cam.add_argument("--pan_direction", choices=PAN_DIRECTIONS, default=None, help="default horizontal")
+    cam.add_argument("--zoom_in_pct", type=float, default=None, help="share of the video spent zooming in (default 0.25)")
+    cam.add_argument("--zoom_pulse", type=float, default=0.0, help="amplitude of the zoom pulse (0 = off)")
+    cam.add_argument("--zoom_pulse_freq", type=float, default=None, help="pulse cycles per video (default 2.0)")
+    cam.add_argument("--hue_rotate", type=float, default=0.0, help="total hue rotation in degrees over the video")
+    cam.add_argument("--temporal_smooth", type=int, default=0, help="temporal smoothing kernel in frames (0 = off)")
+    cam.add_argument("--zoom", type=float, default=None, help="static centre zoom of every still before the pan scale")
     return ap
+
+
+def camera_argument_error(args) -> Optional[str]:
+    """The message of a bad combination of camera flags, or None.  No device is touched."""
+    given = [name for name, on in (
+        ("--pan_direction", args.pan_direction is not None), ("--zoom_in_pct", args.zoom_in_pct is not None),
+        ("--zoom_pulse", args.zoom_pulse != 0), ("--zoom_pulse_freq", args.zoom_pulse_freq is not None),
+        ("--hue_rotate", args.hue_rotate != 0), ("--temporal_smooth", args.temporal_smooth != 0),
+        ("--zoom", args.zoom is not None)) if on]
+    if args.pan_zoom is None:
+        return f"{', '.join(given)} need(s) --pan_zoom > 1 (the camera stage runs only then)" if given else None
+    if not args.pan_zoom > 1.0:
+        return f"--pan_zoom must be greater than 1, got {args.pan_zoom}"
+    if args.zoom_in_pct is not None and not 0.0 <= args.zoom_in_pct <= 1.0:
+        return f"--zoom_in_pct must lie in [0, 1], got {args.zoom_in_pct}"
+    if args.zoom_pulse < 0 or not args.zoom_pulse <= 1.0:
+        return f"--zoom_pulse must lie in [0, 1], got {args.zoom_pulse}"
+    if not 0 <= args.temporal_smooth <= _lib.NST_CAMERA_MAX_SMOOTH:
+        return f"--temporal_smooth must lie in 0..{_lib.NST_CAMERA_MAX_SMOOTH}, got {args.temporal_smooth}"
+    if args.zoom is not None and not args.zoom >= 1.0:
+        return f"--zoom must be at least 1, got {args.zoom}"
+    return None
+
+
+def pan_size(files: Sequence[Path], tw: int, th: int, pan_zoom: float, zoom: float) -> Tuple[Optional[Tuple[int, int]], Optional[str]]:
+    """((w, h) the stills share at pan size, None) or (None, the error): read from the image headers, no device."""
+    from PIL import Image
+
+    from .camera import pan_geometry
+    size = None
+    for f in files:
+        with Image.open(f) as im:
+            w, h = im.size
+        nw, nh = pan_geometry(w, h, tw, th, pan_zoom, zoom)[4:]
+        if nw < tw or nh < th:
+            return None, f"{f}: its pan size {nw}x{nh} is smaller than the output {tw}x{th}"
+        if size is None:
+            size = (nw, nh)
+        elif (nw, nh) != size:
+            return None, f"{f}: its pan size {nw}x{nh} differs from {files[0]}'s {size[0]}x{size[1]}"
+    return size, None
 
 
 def load_fitted(path: Path, tw: int, th: int, device: torch.device) -> torch.Tensor:
@@ -308,6 +366,55 @@ def _hold(wr: FrameWriter, img: torch.Tensor, n: int, step: int) -> None:
         wr.write(img[None].repeat(min(step, n - s), 1, 1, 1))
 
 
+def _main_camera(args, files: Sequence[Path], k: int, size: Tuple[int, int]) -> int:
+    """The --pan_zoom path: every output frame through the camera stage by its global index."""
+    from . import camera as CAM
+    device = torch.device(args.device)
+    tw, th = args.size
+    zoom = args.zoom if args.zoom is not None else 1.0
+    out_dir = Path(args.output_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    wr = FrameWriter(out_dir, args.output_prefix, args.image_ext, args.jpeg_quality, args.png_writer, args.jpeg_writer)
+    total = total_frames(len(files), k, args.hold_frames, args.hold_end)
+    plan = CAM.frame_plan(total, size, (tw, th), args.pan_zoom, args.pan_direction or "horizontal",
+                          0.25 if args.zoom_in_pct is None else args.zoom_in_pct, args.zoom_pulse,
+                          2.0 if args.zoom_pulse_freq is None else args.zoom_pulse_freq, args.hue_rotate)
+    smooth = CAM.SmoothStream(total, args.temporal_smooth)
+    t, alpha = schedule(k, args.preset, args.easing)
+    step = max(1, min(args.batch, _lib.NST_MORPH_MAX_FRAMES))
+    g = 0
+
+    def emit(frames: torch.Tensor) -> None:
+        nonlocal g
+        n = frames.shape[0]
+        done = smooth.push(CAM.camera_frames(frames, plan[g:g + n], (tw, th)))
+        g += n
+        if done is not None:
+            wr.write(done)
+
+    def hold(img: torch.Tensor, n: int) -> None:
+        for s in range(0, n, step):
+            emit(img[None].repeat(min(step, n - s), 1, 1, 1))
+
+    cur = CAM.load_for_pan(files[0], tw, th, args.pan_zoom, zoom, device)
+    for idx in range(len(files)):
+        hold(cur, args.hold_frames)
+        if idx + 1 < len(files):
+            nxt = CAM.load_for_pan(files[idx + 1], tw, th, args.pan_zoom, zoom, device)
+            fwd, bwd = morph_flows(cur, nxt, args.preset)
+            for s in range(0, k, step):
+                emit(morph_frames(cur, nxt, fwd, bwd, t[s:s + step], alpha[s:s + step]))
+            cur = nxt
+        print(f"[morph] {idx + 1}/{len(files)} {files[idx].name}: {g} frames")
+    hold(cur, args.hold_end)
+    assert g == total and wr.count == total
+    if args.output_video:
+        from .pipeline import assemble_video
+        assemble_video(out_dir, Path(args.output_video), args.fps, None, args.output_prefix)
+    print(f"[morph] wrote {wr.count} frames to {out_dir}")
+    return 0
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     args = build_parser().parse_args(argv)
     files = list_images(args.images_dir, args.images)
@@ -318,6 +425,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if k < 1 or args.hold_frames < 0 or args.hold_end < 0 or args.batch < 1:
         print("[morph] need int(fps * morph_seconds) >= 1, hold counts >= 0 and --batch >= 1", file=sys.stderr)
         return 2
+    err = camera_argument_error(args)
+    if err is None and args.pan_zoom is not None:
+        size, err = pan_size(files, args.size[0], args.size[1], args.pan_zoom, args.zoom if args.zoom is not None else 1.0)
+    if err is not None:
+        print(f"[morph] {err}", file=sys.stderr)
+        return 2
+    if args.pan_zoom is not None:
+        return _main_camera(args, files, k, size)
     device = torch.device(args.device)
     tw, th = args.size
     out_dir = Path(args.output_dir)
