@@ -666,6 +666,48 @@ int nst_camera_frames_u8(const uint8_t* in, int n, int h, int w, const nst_camer
                          const int32_t* xofs, const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef,
                          int table_slots, uint8_t* out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Style morph: the weight-ladder blend of scripts/style_morph.py (create_video :216-298, interpolate_ladder
+ * :105-118, the filters :42-59; style_morph.py here) ----
+ * n output frames [n,h,w,3] u8 RGB from a bank of u8 RGB images [n_bank,h,w,3] (device; image i at byte i*h*w*3, any
+ * alignment) and a host table of n descriptors; any n >= 1, the call splits it into launches itself.  Per channel, in
+ * fp32 without contraction, in this order:
+ *   S  = (float)bank[orig] * orig_w
+ *   per term:  sf = hi < 0 ? (float)bank[lo] : (float)bank[lo] * w_lo + (float)bank[hi] * w_hi;  S = S + sf * weight
+ *   v  = n_sides == 2 ? S0 * fade[0] + S1 * fade[1] : S0
+ *   u8 = (uint8)min(max(v, 0), 255)                       truncated, as np.clip(...).astype(np.uint8)
+ * then the filter on the u8 pixel: NST_SM_FILTER_SAT 8-bit RGB2HSV (as nst_camera_hue_u8), s' = (uint8)clip((float)s *
+ * fparam[0], 0, 255), HSV2RGB; NST_SM_FILTER_VIBRANCE boost = fparam[0] + fparam[1] * ((float)s / 255.f) (an IEEE
+ * division), s' = (uint8)clip((float)s * boost, 0, 255); NST_SM_FILTER_WARM R * fparam[0], G * fparam[1], B * fparam[2],
+ * each clipped to 0..255 and truncated.  The arithmetic is the reference's own numpy float32 code; only the two
+ * cvtColor calls are restated (parity unpinned, as the camera stage).
+ * NST_E_INVALID: n < 1, a null pointer, an index outside 0..n_bank-1 (hi < 0 is the one-rung form), n_terms outside
+ * 0..NST_STYLE_MORPH_MAX_STYLES, n_sides outside 1..2, an unknown filter, out overlapping the bank; NST_E_SHAPE: h or
+ * w outside 1..32768.  Everything is checked before the first launch. */
+#define NST_STYLE_MORPH_MAX_STYLES 8
+#define NST_SM_FILTER_NONE 0
+#define NST_SM_FILTER_SAT 1
+#define NST_SM_FILTER_VIBRANCE 2
+#define NST_SM_FILTER_WARM 3
+typedef struct nst_style_morph_term {
+  int lo, hi;
+  float w_lo, w_hi, weight;
+} nst_style_morph_term;
+typedef struct nst_style_morph_side {
+  int orig;
+  float orig_w;
+  int n_terms;
+  nst_style_morph_term term[NST_STYLE_MORPH_MAX_STYLES];
+} nst_style_morph_side;
+typedef struct nst_style_morph_frame {
+  int n_sides;
+  float fade[2];
+  nst_style_morph_side side[2];
+  int filter;
+  float fparam[3];
+} nst_style_morph_frame;
+int nst_style_morph_frames(const uint8_t* bank, int n_bank, int h, int w, const nst_style_morph_frame* frames, int n,
+                           uint8_t* out, void* stream);
+
 /* ---- PNG encode on the owner rank (pipeline.py:2099-2119 `Image.fromarray(out).save(path)`, the reference's
  * default --image_ext png at :2170) ----
  * n u8 frames [n,h,w,c] (c = 1 grey, 3 RGB, 4 RGBA; device) -> n complete PNG files, file j at out + j*out_stride,

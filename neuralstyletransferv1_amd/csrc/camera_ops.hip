@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <string>
 
+#include "hsv_common.h"
 #include "nst_hip.h"
 #include "nst_internal.h"
 
@@ -162,30 +163,11 @@ __device__ __forceinline__ void lanczos_px(const uint8_t* __restrict__ img, int 
   }
 }
 
-// rint(num / den) half-to-even for positive integers: what rint of the double quotient gives (a quotient that is
-// not a tie is at least 1 / (2 den) away from one)
-__device__ __forceinline__ int div_rint(int num, int den) {
-  int q = num / den;
-  const int r2 = 2 * (num - q * den);
-  if (r2 > den || (r2 == den && (q & 1))) ++q;
-  return q;
-}
-
-__device__ __forceinline__ int sat_u8f(float v) { return (int)fminf(fmaxf(rintf(v), 0.f), 255.f); }
-
 // apply_hue_shift on one RGB pixel: cv2's 8-bit BGR2HSV, the fp32 remainder numpy takes, HSV2BGR's float path
+// (both conversions in hsv_common.h)
 __device__ __forceinline__ void hue_px(int* rgb, float half) {
-  const int r = rgb[0], g = rgb[1], b = rgb[2];
-  const int v = max(r, max(g, b)), vmin = min(r, min(g, b));
-  const int diff = v - vmin;
-  const int sdiv = v ? div_rint(255 << 12, v) : 0;
-  const int hdiv = diff ? div_rint(122880, diff) : 0;  // (180 << 12) / (6 diff)
-  const int s = (diff * sdiv + 2048) >> 12;
-  int hn = v == r ? g - b : (v == g ? b - r + 2 * diff : r - g + 4 * diff);
-  int hh = (hn * hdiv + 2048) >> 12;
-  if (hh < 0) hh += 180;
-  hh = min(max(hh, 0), 255);
-  const int s8 = s & 255;
+  int hh, s8, v;
+  rgb_to_hsv8(rgb[0], rgb[1], rgb[2], &hh, &s8, &v);
   // np.remainder(float32(h) + half, 180): fmod, then the divisor's sign
   float m = fmodf((float)hh + half, 180.f);
   if (m != 0.f) {
@@ -193,37 +175,7 @@ __device__ __forceinline__ void hue_px(int* rgb, float half) {
   } else {
     m = 0.f;
   }
-  const int h8 = (int)m;  // 0 .. 180
-  const float vf = (float)v * (1.f / 255.f);
-  float bo, go, ro;
-  if (s8 == 0) {
-    bo = go = ro = vf;
-  } else {
-    const float sf = (float)s8 * (1.f / 255.f);
-    float h = (float)h8 * (6.f / 180.f);
-    h = fmodf(h, 6.f);
-    int sector = (int)floorf(h);
-    h -= (float)sector;
-    if ((unsigned)sector >= 6u) {
-      sector = 0;
-      h = 0.f;
-    }
-    float tab[4];
-    tab[0] = vf;
-    tab[1] = vf * (1.f - sf);
-    tab[2] = vf * (1.f - sf * h);
-    tab[3] = vf * (1.f - sf * (1.f - h));
-    // sector_data {1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}: the (b, g, r) picks
-    const int pb = sector == 0 || sector == 1 ? 1 : (sector == 2 ? 3 : (sector == 5 ? 2 : 0));
-    const int pg = sector == 0 ? 3 : (sector == 1 || sector == 2 ? 0 : (sector == 3 ? 2 : 1));
-    const int pr = sector == 0 || sector == 5 ? 0 : (sector == 1 ? 2 : (sector == 4 ? 3 : 1));
-    bo = tab[pb];
-    go = tab[pg];
-    ro = tab[pr];
-  }
-  rgb[0] = sat_u8f(ro * 255.f);
-  rgb[1] = sat_u8f(go * 255.f);
-  rgb[2] = sat_u8f(bo * 255.f);
+  hsv8_to_rgb((int)m, s8, v, rgb);  // (int)m: 0 .. 180
 }
 
 // ---- the single stages (a) - (d), one thread per output pixel: what the tests and camera.py's wrappers call ----
