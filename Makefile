@@ -9,7 +9,7 @@ BUILD := build/obj
 SLP ?= -fno-slp-vectorize
 CXXFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off $(SLP) -Wall -Wno-unused-function \
             -Iinclude -I$(CSRC)
-SRCS := $(CSRC)/conv_bf16.hip $(CSRC)/conv_f16.hip $(CSRC)/conv_bf16_wl.hip $(CSRC)/conv_wphase.hip $(CSRC)/conv_ws2.hip $(CSRC)/conv_ws9.hip $(CSRC)/conv_ws1s.hip $(CSRC)/conv_out9.hip $(CSRC)/conv_prep.hip $(CSRC)/conv_f32.hip $(CSRC)/conv_f32s.hip $(CSRC)/conv_vgg.hip $(CSRC)/nst_ops.hip $(CSRC)/t7_ops.hip $(CSRC)/vgg_ops.hip $(CSRC)/conv_gemm.hip $(CSRC)/seg_ops.hip $(CSRC)/seg_drn_head.hip $(CSRC)/region_ops.hip $(CSRC)/flow_ops.hip $(CSRC)/morph_ops.hip $(CSRC)/camera_ops.hip $(CSRC)/style_morph_ops.hip $(CSRC)/dis_ops.hip $(CSRC)/png_enc.hip $(CSRC)/jpeg_dec.hip $(CSRC)/jpeg_enc.hip $(CSRC)/nst_api.cpp $(CSRC)/vgg_gatys.cpp $(CSRC)/seg_deeplab.cpp $(CSRC)/region_api.cpp $(CSRC)/flow_api.cpp $(CSRC)/jpeg_entropy.cpp
+SRCS := $(CSRC)/conv_bf16.hip $(CSRC)/conv_f16.hip $(CSRC)/conv_bf16_wl.hip $(CSRC)/conv_wphase.hip $(CSRC)/conv_ws2.hip $(CSRC)/conv_ws9.hip $(CSRC)/conv_ws1s.hip $(CSRC)/conv_out9.hip $(CSRC)/conv_prep.hip $(CSRC)/conv_f32.hip $(CSRC)/conv_f32s.hip $(CSRC)/conv_vgg.hip $(CSRC)/nst_ops.hip $(CSRC)/t7_ops.hip $(CSRC)/vgg_ops.hip $(CSRC)/conv_gemm.hip $(CSRC)/seg_ops.hip $(CSRC)/seg_drn_head.hip $(CSRC)/region_ops.hip $(CSRC)/blur_ops.hip $(CSRC)/flow_ops.hip $(CSRC)/morph_ops.hip $(CSRC)/camera_ops.hip $(CSRC)/style_morph_ops.hip $(CSRC)/dis_ops.hip $(CSRC)/png_enc.hip $(CSRC)/jpeg_dec.hip $(CSRC)/jpeg_enc.hip $(CSRC)/nst_api.cpp $(CSRC)/vgg_gatys.cpp $(CSRC)/seg_deeplab.cpp $(CSRC)/region_api.cpp $(CSRC)/flow_api.cpp $(CSRC)/jpeg_entropy.cpp
 # conv_wst16.hip (the residual trunk): nine objects from one source (NST_W16_PART: 0..7 two explicitly instantiated
 # kernels each, ~2-3 min per kernel, compiled in parallel; 8 the launchers and the table)
 W16_OBJS := $(patsubst %,$(BUILD)/conv_wst16_p%.hip.o,0 1 2 3 4 5 6 7 8)
@@ -18,7 +18,7 @@ LIB := $(PKG)/libnst_hip.so
 
 all: $(LIB)
 
-$(BUILD)/%.hip.o: $(CSRC)/%.hip $(CSRC)/conv_impl.h $(CSRC)/conv_ws_common.h $(CSRC)/conv_tab16.h $(CSRC)/conv_tab32.h $(CSRC)/nst_internal.h $(CSRC)/seg_internal.h $(CSRC)/post_common.h $(CSRC)/region_internal.h $(CSRC)/flow_internal.h include/nst_hip.h
+$(BUILD)/%.hip.o: $(CSRC)/%.hip $(CSRC)/conv_impl.h $(CSRC)/conv_ws_common.h $(CSRC)/conv_tab16.h $(CSRC)/conv_tab32.h $(CSRC)/nst_internal.h $(CSRC)/seg_internal.h $(CSRC)/post_common.h $(CSRC)/region_internal.h $(CSRC)/flow_internal.h $(CSRC)/blur_internal.h include/nst_hip.h
 	@mkdir -p $(BUILD)
 	$(if $(NOSCRATCH),$(HIPCC) $(CXXFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $@.rem && python3 tools/check_scratch.py $@.rem || { rm -f $@; exit 1; },$(HIPCC) $(CXXFLAGS) -c $< -o $@)
 
@@ -42,7 +42,7 @@ $(BUILD)/conv_ws2.hip.o: CXXFLAGS += -mllvm -pragma-unroll-threshold=5000000
 $(BUILD)/conv_ws9.hip.o: CXXFLAGS += -mllvm -pragma-unroll-threshold=5000000
 $(BUILD)/conv_ws1s.hip.o: CXXFLAGS += -mllvm -pragma-unroll-threshold=5000000
 
-$(BUILD)/%.cpp.o: $(CSRC)/%.cpp $(CSRC)/nst_internal.h $(CSRC)/seg_internal.h $(CSRC)/post_common.h $(CSRC)/region_internal.h $(CSRC)/flow_internal.h include/nst_hip.h
+$(BUILD)/%.cpp.o: $(CSRC)/%.cpp $(CSRC)/nst_internal.h $(CSRC)/seg_internal.h $(CSRC)/post_common.h $(CSRC)/region_internal.h $(CSRC)/flow_internal.h $(CSRC)/blur_internal.h include/nst_hip.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(CXXFLAGS) -x hip -c $< -o $@
 
@@ -50,6 +50,8 @@ $(BUILD)/%.cpp.o: $(CSRC)/%.cpp $(CSRC)/nst_internal.h $(CSRC)/seg_internal.h $(
 $(BUILD)/jpeg_dec.hip.o $(BUILD)/jpeg_enc.hip.o $(BUILD)/jpeg_entropy.cpp.o: $(CSRC)/jpeg_common.h
 # the camera's hue rotation and the style morph's saturation filters share cv2's 8-bit HSV conversions
 $(BUILD)/camera_ops.hip.o $(BUILD)/style_morph_ops.hip.o: $(CSRC)/hsv_common.h
+# the blurs, the flows' gradients and warps and the mask feathers share OpenCV's two mirrored border rules
+$(BUILD)/blur_ops.hip.o $(BUILD)/dis_ops.hip.o $(BUILD)/morph_ops.hip.o $(BUILD)/nst_ops.hip.o $(BUILD)/region_ops.hip.o: $(CSRC)/border_common.h
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
@@ -61,7 +63,7 @@ ASAN_OBJS := $(patsubst %,build/asan/%.o,$(ASAN_HOST))
 ASAN_BIN := tools/asan/nst_asan_driver
 ASAN_FLAGS := -Xarch_host -fsanitize=address -Xarch_host -fno-omit-frame-pointer
 
-build/asan/%.cpp.o: $(CSRC)/%.cpp $(CSRC)/nst_internal.h $(CSRC)/seg_internal.h $(CSRC)/post_common.h $(CSRC)/region_internal.h $(CSRC)/flow_internal.h include/nst_hip.h
+build/asan/%.cpp.o: $(CSRC)/%.cpp $(CSRC)/nst_internal.h $(CSRC)/seg_internal.h $(CSRC)/post_common.h $(CSRC)/region_internal.h $(CSRC)/flow_internal.h $(CSRC)/blur_internal.h include/nst_hip.h
 	@mkdir -p build/asan
 	$(HIPCC) $(CXXFLAGS) $(ASAN_FLAGS) -x hip -c $< -o $@
 

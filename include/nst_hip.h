@@ -528,7 +528,9 @@ int nst_region_resize(const float* y, int n, int h, int w, int preset, int fit_h
 int nst_gray_u8(const uint8_t* rgb, int n, int h, int w, uint8_t* gray, void* stream);
 /* cv2.calcOpticalFlowFarneback(prev, next, None, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, 0)
  * (pipeline.py:1896-1899 passes 0.5, 3, 15, 3, 5, 1.1): OpenCV's optflowgf.cpp restated (cv2 absent: parity
- * unpinned).  prev/next u8 [h,w] device, flow f32 [h,w,2] = (dx, dy); scratch per nst_flow_scratch_floats. */
+ * unpinned).  prev/next u8 [h,w] device, flow f32 [h,w,2] = (dx, dy); scratch per nst_flow_scratch_floats.  This is
+ * nst_flow_farneback_ex (below) with n = 1 and flags = 0, the same code: a pyramid whose coarsest level needs 64 to
+ * 511 pre-blur taps, which used to fail at launch, now runs; a deeper one -> NST_E_SHAPE. */
 int nst_flow_scratch_floats(int h, int w, size_t* out);
 int nst_flow_farneback(const uint8_t* prev, const uint8_t* next, int h, int w, double pyr_scale, int levels,
                        int winsize, int iterations, int poly_n, double poly_sigma, float* flow, float* scratch,
@@ -565,7 +567,7 @@ int nst_motion_alpha(const float* flow, int h, int w, float motion_norm, double 
  * scripts/morph_v2.py:365-468; morph.py).  cv2 absent: every restatement below is parity unpinned. ---- */
 /* cv2.calcOpticalFlowFarneback(prev, next, None, ..., flags) for n independent pairs in the same launches: prev/next
  * u8 [n,h,w] device, flow f32 [n,h,w,2]; scratch per nst_flow_scratch_floats_ex(n, h, w).  flags = 0 (the box window
- * of nst_flow_farneback; n = 1 gives its flow bit for bit) or NST_FLOW_GAUSSIAN (cv2.OPTFLOW_FARNEBACK_GAUSSIAN,
+ * of nst_flow_farneback, which is this entry point at n = 1) or NST_FLOW_GAUSSIAN (cv2.OPTFLOW_FARNEBACK_GAUSSIAN,
  * FarnebackUpdateFlow_GaussianBlur restated): m = winsize/2 (<= 63), sigma = m*0.3, taps k[0] = 1,
  * k[i] = (float)exp(-i*i/(2*sigma*sigma)), normalised by s = 1 + 2*sum k[i] in double; the 5 fields of M summed in
  * fp32 down the columns then along the rows, v = M[y]*k[0], v += (M[y-i] + M[y+i])*k[i] for i = 1..m (replicated

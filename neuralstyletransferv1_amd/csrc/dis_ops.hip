@@ -21,6 +21,7 @@
 #include <cfloat>
 #include <math.h>
 
+#include "border_common.h"
 #include "flow_internal.h"
 
 namespace nst {
@@ -49,11 +50,6 @@ __global__ __launch_bounds__(256) void pad_rep_kernel(const uint8_t* __restrict_
   out[i] = in[((size_t)f * h + sy) * w + sx];
 }
 
-__device__ __forceinline__ int refl101(int p, int n) {
-  p = p < 0 ? -p : p;
-  return p >= n ? 2 * n - 2 - p : p;
-}
-
 // spatialGradient (3x3 Sobel, BORDER_REFLECT_101) -> int16
 __global__ __launch_bounds__(256) void sobel_kernel(const uint8_t* __restrict__ I, int n, int h, int w,
                                                     int16_t* __restrict__ gx, int16_t* __restrict__ gy) {
@@ -63,7 +59,8 @@ __global__ __launch_bounds__(256) void sobel_kernel(const uint8_t* __restrict__ 
   const size_t r = i / w;
   const int y = (int)(r % h), f = (int)(r / h);
   const uint8_t* P = I + (size_t)f * h * w;
-  const int ym = refl101(y - 1, h), yp = refl101(y + 1, h), xm = refl101(x - 1, w), xp = refl101(x + 1, w);
+  const int ym = border_reflect101(y - 1, h), yp = border_reflect101(y + 1, h);
+  const int xm = border_reflect101(x - 1, w), xp = border_reflect101(x + 1, w);
   auto at = [&](int yy, int xx) { return (int)P[(size_t)yy * w + xx]; };
   const int dxm = at(ym, xp) - at(ym, xm), dx0 = at(y, xp) - at(y, xm), dxp = at(yp, xp) - at(yp, xm);
   const int dym = at(yp, xm) - at(ym, xm), dy0 = at(yp, x) - at(ym, x), dyp = at(yp, xp) - at(ym, xp);

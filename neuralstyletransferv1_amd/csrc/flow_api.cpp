@@ -1,6 +1,7 @@
 // flow_api.cpp — C ABI of the temporal stage (include/nst_hip.h "Temporal stage").
 #include <string>
 
+#include "blur_internal.h"
 #include "flow_internal.h"
 #include "nst_hip.h"
 #include "nst_internal.h"
@@ -26,20 +27,33 @@ int nst_gray_u8(const uint8_t* rgb, int n, int h, int w, uint8_t* gray, void* st
 
 int nst_flow_scratch_floats(int h, int w, size_t* out) {
   if (h <= 0 || w <= 0 || !out) { set_error("nst_flow_scratch_floats: invalid arguments"); return NST_E_INVALID; }
-  *out = farneback_scratch_floats(h, w);
+  *out = farneback_scratch_floats_ex(1, h, w);
   return NST_OK;
+}
+
+// the pyramid's coarsest level sets the widest pre-blur; one wider than the blur's tap table is refused
+static int check_pyramid(const char* who, int h, int w, double pyr_scale, int levels) {
+  const int ksz = farneback_max_ksize(h, w, pyr_scale, levels);
+  if (ksz <= BLUR_MAX_TAPS) return NST_OK;
+  set_error(std::string(who) + ": the pyramid of a " + std::to_string(w) + "x" + std::to_string(h) + " frame at " +
+            std::to_string(levels) + " levels needs a " + std::to_string(ksz) + "-tap pre-blur (at most " +
+            std::to_string(BLUR_MAX_TAPS) + ")");
+  return NST_E_SHAPE;
 }
 
 int nst_flow_farneback(const uint8_t* prev, const uint8_t* next, int h, int w, double pyr_scale, int levels,
                        int winsize, int iterations, int poly_n, double poly_sigma, float* flow, float* scratch,
                        size_t scratch_floats, void* stream) {
   if (!prev || !next || !flow || !scratch || h < 2 || w < 2 || !(pyr_scale > 0 && pyr_scale < 1) || levels < 0 ||
-      winsize < 1 || (winsize & 1) == 0 || iterations < 1 || poly_n < 1 || poly_n > 8 || scratch_floats < farneback_scratch_floats(h, w)) {
+      winsize < 1 || (winsize & 1) == 0 || iterations < 1 || poly_n < 1 || poly_n > 8 ||
+      scratch_floats < farneback_scratch_floats_ex(1, h, w)) {
     set_error("nst_flow_farneback: invalid arguments (odd winsize, poly_n 1..8, scratch per nst_flow_scratch_floats)");
     return NST_E_INVALID;
   }
-  FL_LAUNCH(launch_farneback(prev, next, h, w, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flow, scratch,
-                             (hipStream_t)stream),
+  const int rc = check_pyramid("nst_flow_farneback", h, w, pyr_scale, levels);
+  if (rc != NST_OK) return rc;
+  FL_LAUNCH(launch_farneback_ex(prev, next, 1, h, w, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, false,
+                                flow, scratch, (hipStream_t)stream),
             "farneback");
   return NST_OK;
 }
@@ -143,12 +157,8 @@ int nst_flow_farneback_ex(const uint8_t* prev, const uint8_t* next, int n, int h
               "window, poly_n 1..8, scratch per nst_flow_scratch_floats_ex)");
     return NST_E_INVALID;
   }
-  const int ksz = farneback_max_ksize(h, w, pyr_scale, levels);
-  if (ksz > 511) {
-    set_error("nst_flow_farneback_ex: the pyramid of a " + std::to_string(w) + "x" + std::to_string(h) + " frame at " +
-              std::to_string(levels) + " levels needs a " + std::to_string(ksz) + "-tap pre-blur (at most 511)");
-    return NST_E_SHAPE;
-  }
+  const int rc = check_pyramid("nst_flow_farneback_ex", h, w, pyr_scale, levels);
+  if (rc != NST_OK) return rc;
   FL_LAUNCH(launch_farneback_ex(prev, next, n, h, w, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma,
                                 flags == NST_FLOW_GAUSSIAN, flow, scratch, (hipStream_t)stream),
             "farneback_ex");

@@ -8,10 +8,6 @@
 namespace nst {
 
 hipError_t launch_gray(const uint8_t* rgb, size_t npix, uint8_t* gray, hipStream_t st);
-size_t farneback_scratch_floats(int h, int w);
-hipError_t launch_farneback(const uint8_t* prev, const uint8_t* next, int h, int w, double pyr_scale, int levels,
-                            int winsize, int iterations, int poly_n, double poly_sigma, float* flow, float* scratch,
-                            hipStream_t st);
 // cv2.resize INTER_AREA of n u8 images [h][w][ch] -> [oh][ow][ch] (downscaling: oh <= h, ow <= w)
 // DIS optical flow (dis_ops.hip): scratch bytes for n pairs of h x w frames; 0 = ok, -1 frame too small for
 // PRESET_FAST's pyramid, -2 too wide for the inverse search's LDS stripe
@@ -27,16 +23,16 @@ hipError_t launch_flow_fuse(const float* curr, const float* prev, const float* f
                             float* out, hipStream_t st);
 hipError_t launch_motion_alpha(const float* flow, int h, int w, float norm, double sigma, float max_alpha, float span,
                                float* alpha, float* tmp, hipStream_t st);
-// Farneback for n pairs in the same launches (prev/next [n,h,w], flow [n,h,w,2]); gaussian: the Gaussian window
-// (OPTFLOW_FARNEBACK_GAUSSIAN, winsize / 2 <= 63) instead of the box
+// Farneback for n pairs in the same launches (prev/next [n,h,w], flow [n,h,w,2]; the only implementation:
+// nst_flow_farneback is n = 1); gaussian: the Gaussian window (OPTFLOW_FARNEBACK_GAUSSIAN, winsize / 2 <= 63)
+// instead of the box
 size_t farneback_scratch_floats_ex(int n, int h, int w);
 hipError_t launch_farneback_ex(const uint8_t* prev, const uint8_t* next, int n, int h, int w, double pyr_scale,
                                int levels, int winsize, int iterations, int poly_n, double poly_sigma, bool gaussian,
                                float* flow, float* scratch, hipStream_t st);
-// the widest pyramid pre-blur (taps) launch_farneback_ex would run for these arguments; it takes at most 511
+// the widest pyramid pre-blur (taps) launch_farneback_ex would run for these arguments; it takes at most
+// BLUR_MAX_TAPS (blur_internal.h)
 int farneback_max_ksize(int h, int w, double pyr_scale, int levels);
-// cv2.getGaussianKernel(n, sigma, CV_32F) into t[n] (n <= 63)
-void gaussian_taps_f32(int n, double sigma, float* t);
 // morph_ops.hip
 hipError_t launch_gray_cv(const uint8_t* rgb, size_t npix, uint8_t* gray, hipStream_t st);
 hipError_t launch_gauss_u8(const uint8_t* in, int n, int h, int w, uint8_t* out, hipStream_t st);

@@ -3,10 +3,12 @@
 //   * grayscale of the content frame (pipeline.py:1100 pil_rgb.convert("L"): Pillow's integer luma)
 //   * dense optical flow cv2.calcOpticalFlowFarneback(prev, next, None, 0.5, 3, 15, 3, 5, 1.1, 0) restated
 //     after OpenCV's optflowgf.cpp (cv2 is not installed here: parity unpinned): per pyramid level the
-//     images are Gaussian-smoothed and resized, expanded into quadratic polynomials (FarnebackPolyExp,
-//     separable 1-D Gaussian-weighted moments, n = 5, sigma = 1.1), then `iterations` rounds of
-//     UpdateMatrices + a 15 x 15 box blur of the 5 matrix fields + the 2x2 solve; coarse-to-fine with the
-//     flow resized x 1/pyr_scale between levels;
+//     images are Gaussian-smoothed (blur_ops.hip) and resized, expanded into quadratic polynomials
+//     (FarnebackPolyExp, separable 1-D Gaussian-weighted moments, n = 5, sigma = 1.1), then `iterations` rounds
+//     of UpdateMatrices + a 15 x 15 box blur (or, with OPTFLOW_FARNEBACK_GAUSSIAN, a Gaussian window) of the 5
+//     matrix fields + the 2x2 solve; coarse-to-fine with the flow resized x 1/pyr_scale between levels.  One
+//     implementation, launch_farneback_ex, for n pairs in the same launches: the pipeline's --flow_ema runs it
+//     with one pair, the morph with its forward and backward pair;
 //   * the flow-guided EMA: prev styled frame warped by cv2.remap(INTER_LINEAR, BORDER_REPLICATE) of
 //     grid + flow (restated), fused = clip(a * curr + (1 - a) * warped);
 //   * the motion-adaptive blend alpha: clip(|flow| / 8) blurred (cv2.GaussianBlur sigma 3), then
@@ -17,6 +19,7 @@
 
 #include <algorithm>
 
+#include "blur_internal.h"
 #include "flow_internal.h"
 
 namespace nst {
@@ -39,69 +42,12 @@ __global__ __launch_bounds__(256) void u8_to_f32_kernel(const uint8_t* __restric
   if (i < n) o[i] = (float)a[i];
 }
 
-// separable Gaussian with BORDER_REFLECT_101, taps in a kernel argument (cv2.GaussianBlur on a float image)
-struct Taps {
-  int n;
-  float t[64];
-};
-
-__device__ __forceinline__ int refl101(int p, int n) {
-  if (n == 1) return 0;
-  while (p < 0 || p >= n) p = p < 0 ? -p : 2 * n - 2 - p;
-  return p;
-}
-
-__global__ __launch_bounds__(256) void gauss_rows_kernel(const float* __restrict__ in, int h, int w, Taps tp,
-                                                         float* __restrict__ out) {
-  const size_t plane = (size_t)blockIdx.z * h * w;
-  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
-  const int r = tp.n / 2;
-  const float* row = in + plane + (size_t)y * w;
-  float acc = 0.f;
-  for (int j = 0; j < tp.n; ++j) acc = acc + tp.t[j] * row[refl101(x + j - r, w)];
-  out[plane + (size_t)y * w + x] = acc;
-}
-
-__global__ __launch_bounds__(256) void gauss_cols_kernel(const float* __restrict__ in, int h, int w, Taps tp,
-                                                         float* __restrict__ out) {
-  const size_t plane = (size_t)blockIdx.z * h * w;
-  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
-  const int r = tp.n / 2;
-  float acc = 0.f;
-  for (int j = 0; j < tp.n; ++j) acc = acc + tp.t[j] * in[plane + (size_t)refl101(y + j - r, h) * w + x];
-  out[plane + (size_t)y * w + x] = acc;
-}
-
-// cv2.getGaussianKernel(n, sigma, CV_32F): sigma <= 0 and n <= 7 takes the fixed small table
-static Taps gaussian_taps(int n, double sigma) {
-  Taps tp;
-  tp.n = n;
-  if (sigma <= 0 && n == 3) {
-    tp.t[0] = 0.25f; tp.t[1] = 0.5f; tp.t[2] = 0.25f;
-    return tp;
-  }
-  if (sigma <= 0) sigma = ((n - 1) * 0.5 - 1) * 0.3 + 0.8;
-  const double s2 = -0.5 / (sigma * sigma);
-  double sum = 0;
-  double v[64];
-  for (int i = 0; i < n; ++i) {
-    const double x = i - (n - 1) * 0.5;
-    v[i] = std::exp(s2 * x * x);
-    sum += v[i];
-  }
-  for (int i = 0; i < n; ++i) tp.t[i] = (float)(v[i] / sum);
-  return tp;
-}
-
-hipError_t launch_gauss(float* planes, int k, int h, int w, int ksize, double sigma, float* tmp, hipStream_t st) {
-  if (ksize > 63) return hipErrorInvalidValue;
-  const Taps tp = gaussian_taps(ksize, sigma);
-  const dim3 g((unsigned)((w + 255) / 256), (unsigned)h, (unsigned)k);
-  hipLaunchKernelGGL(gauss_rows_kernel, g, dim3(256), 0, st, planes, h, w, tp, tmp);
-  hipLaunchKernelGGL(gauss_cols_kernel, g, dim3(256), 0, st, tmp, h, w, tp, planes);
-  return hipGetLastError();
+// cv2.GaussianBlur(planes, (ksize, ksize), sigma) of k float planes, in place through tmp
+static hipError_t gauss_blur(float* planes, int k, int h, int w, int ksize, double sigma, float* tmp, hipStream_t st) {
+  if (ksize > BLUR_MAX_TAPS) return hipErrorInvalidValue;
+  float taps[BLUR_MAX_TAPS];
+  gaussian_taps_f32(ksize, sigma, taps);
+  return launch_sep_blur_f32(planes, k, h, w, taps, ksize, tmp, st);
 }
 
 // cv2.resize(INTER_LINEAR) of float planes with c interleaved channels: fx = (dx + 0.5) * scale - 0.5, taps
@@ -233,193 +179,6 @@ static PolyTab poly_tab(int n, double sigma) {
   pt.ig11 = 1.0 / b;
   pt.ig55 = 1.0 / d;
   return pt;
-}
-
-// FarnebackUpdateMatrices
-__global__ __launch_bounds__(256) void update_matrices_kernel(const float* __restrict__ R0, const float* __restrict__ R1,
-                                                              const float* __restrict__ flow, int h, int w,
-                                                              float* __restrict__ M) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)h * w) return;
-  const int x = (int)(i % w), y = (int)(i / w);
-  const float border[5] = {0.14f, 0.14f, 0.4472f, 0.4472f, 0.4472f};
-  const float dx = flow[2 * i], dy = flow[2 * i + 1];
-  float fx = (float)x + dx, fy = (float)y + dy;
-  const int x1 = (int)floorf(fx), y1 = (int)floorf(fy);
-  fx -= (float)x1;
-  fy -= (float)y1;
-  const float* r0 = R0 + i * 5;
-  float r2, r3, r4, r5, r6;
-  if ((unsigned)x1 < (unsigned)(w - 1) && (unsigned)y1 < (unsigned)(h - 1)) {
-    const float a00 = (1.f - fx) * (1.f - fy), a01 = fx * (1.f - fy), a10 = (1.f - fx) * fy, a11 = fx * fy;
-    const float* p = R1 + ((size_t)y1 * w + x1) * 5;
-    const size_t s1 = (size_t)w * 5;
-    float v[5];
-#pragma unroll
-    for (int c = 0; c < 5; ++c) v[c] = a00 * p[c] + a01 * p[5 + c] + a10 * p[s1 + c] + a11 * p[s1 + 5 + c];
-    r2 = v[0]; r3 = v[1];
-    r4 = (r0[2] + v[2]) * 0.5f;
-    r5 = (r0[3] + v[3]) * 0.5f;
-    r6 = (r0[4] + v[4]) * 0.25f;
-  } else {
-    r2 = r3 = 0.f;
-    r4 = r0[2];
-    r5 = r0[3];
-    r6 = r0[4] * 0.5f;
-  }
-  r2 = (r0[0] - r2) * 0.5f;
-  r3 = (r0[1] - r3) * 0.5f;
-  r2 += r4 * dy + r6 * dx;
-  r3 += r6 * dy + r5 * dx;
-  if ((unsigned)(x - 5) >= (unsigned)(w - 10) || (unsigned)(y - 5) >= (unsigned)(h - 10)) {
-    const float sc = (x < 5 ? border[x] : 1.f) * (x >= w - 5 ? border[w - x - 1] : 1.f) * (y < 5 ? border[y] : 1.f) *
-                     (y >= h - 5 ? border[h - y - 1] : 1.f);
-    r2 *= sc; r3 *= sc; r4 *= sc; r5 *= sc; r6 *= sc;
-  }
-  float* m = M + i * 5;
-  m[0] = r4 * r4 + r6 * r6;
-  m[1] = (r4 + r5) * r6;
-  m[2] = r5 * r5 + r6 * r6;
-  m[3] = r4 * r2 + r6 * r3;
-  m[4] = r6 * r2 + r5 * r3;
-}
-
-// FarnebackUpdateFlow_Blur: block_size x block_size box sums of M (rows and columns clamped to the frame)
-// in double, then the 2x2 solve with the 1e-3 regulariser.  As OpenCV sums them: a running vertical sum per
-// column (each step adds the float difference entering - leaving row), then the horizontal window over the
-// vertical sums.  Vertical: one thread per column walks a strip of BOX_ROWS rows; horizontal: a 256-pixel row
-// segment and its halo staged in LDS.
-constexpr int BOX_ROWS = 16;
-
-__global__ __launch_bounds__(256) void box_v_kernel(const float* __restrict__ M, int h, int w, int m,
-                                                    double* __restrict__ vs) {
-  const int x = blockIdx.x * 256 + threadIdx.x;
-  if (x >= w) return;
-  const int y0 = blockIdx.y * BOX_ROWS, y1 = min(h, y0 + BOX_ROWS);
-  auto row = [&](int q) { return M + ((size_t)min(max(q, 0), h - 1) * w + x) * 5; };
-  double s[5] = {0, 0, 0, 0, 0};
-  for (int q = y0 - m; q <= y0 + m; ++q) {
-    const float* p = row(q);
-#pragma unroll
-    for (int c = 0; c < 5; ++c) s[c] += p[c];
-  }
-  for (int y = y0; y < y1; ++y) {
-    if (y > y0) {
-      const float* pa = row(y + m);
-      const float* pd = row(y - m - 1);
-#pragma unroll
-      for (int c = 0; c < 5; ++c) s[c] += pa[c] - pd[c];
-    }
-    double* o = vs + ((size_t)y * w + x) * 5;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) o[c] = s[c];
-  }
-}
-
-__global__ __launch_bounds__(256) void box_h_solve_kernel(const double* __restrict__ vs, int h, int w, int m,
-                                                          double scale, float* __restrict__ flow) {
-  extern __shared__ double seg[];  // (256 + 2m) x 5
-  const int y = blockIdx.y, x0 = blockIdx.x * 256;
-  const int n = 256 + 2 * m;
-  for (int j = threadIdx.x; j < n * 5; j += 256) {
-    const int e = j / 5, c = j - e * 5;
-    const int xs = min(max(x0 - m + e, 0), w - 1);
-    seg[j] = vs[((size_t)y * w + xs) * 5 + c];
-  }
-  __syncthreads();
-  const int x = x0 + threadIdx.x;
-  if (x >= w) return;
-  double s[5] = {0, 0, 0, 0, 0};
-  for (int q = 0; q <= 2 * m; ++q) {
-    const double* p = seg + (threadIdx.x + q) * 5;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) s[c] += p[c];
-  }
-  const size_t i = (size_t)y * w + x;
-  const double g11 = s[0] * scale, g12 = s[1] * scale, g22 = s[2] * scale, h1 = s[3] * scale, h2 = s[4] * scale;
-  const double idet = 1. / (g11 * g22 - g12 * g12 + 1e-3);
-  flow[2 * i] = (float)((g11 * h2 - g12 * h1) * idet);
-  flow[2 * i + 1] = (float)((g22 * h1 - g12 * h2) * idet);
-}
-
-size_t farneback_scratch_floats(int h, int w) {
-  const size_t n = (size_t)h * w;
-  // img f32 x2, tmp x2, I x2, row3 x2 (3ch), R x2 (5ch), M (5ch), vs (5 doubles = 10 floats), flow x2 (2ch)
-  return n * (2 + 2 + 2 + 6 + 10 + 5 + 10 + 4) + 64;
-}
-
-hipError_t launch_farneback(const uint8_t* prev, const uint8_t* next, int h, int w, double pyr_scale, int levels,
-                            int winsize, int iterations, int poly_n, double poly_sigma, float* flow_out, float* scratch,
-                            hipStream_t st) {
-  const size_t n = (size_t)h * w;
-  float* img = scratch;             // 2 planes, full resolution
-  float* tmp = img + 2 * n;         // 2 planes
-  float* I = tmp + 2 * n;           // 2 planes at the level size
-  float* row3 = I + 2 * n;          // 2 x 3ch
-  float* R = row3 + 6 * n;          // 2 x 5ch
-  float* M = R + 10 * n;            // 5ch
-  double* vs = (double*)(M + 5 * n + ((5 * n) & 1));  // 5 doubles per pixel (8-byte aligned)
-  float* fa = (float*)(vs + 5 * n); // 2ch
-  float* fb = fa + 2 * n;           // 2ch
-  const int min_size = 32;
-  int k;
-  double scale = 1;
-  for (k = 0; k < levels; ++k) {
-    scale *= pyr_scale;
-    if (w * scale < min_size || h * scale < min_size) break;
-  }
-  levels = k;
-  const PolyTab pt = poly_tab(poly_n, poly_sigma);
-  const int m = winsize / 2;
-  const double bscale = 1. / (winsize * winsize);
-  float* prev_flow = nullptr;
-  int pw = 0, ph = 0;
-  for (k = levels; k >= 0; --k) {
-    scale = 1;
-    for (int i = 0; i < k; ++i) scale *= pyr_scale;
-    const double sigma = (1. / scale - 1) * 0.5;
-    int ksz = ((int)std::nearbyint(sigma * 5)) | 1;
-    ksz = std::max(ksz, 3);
-    const int lw = (int)std::nearbyint(w * scale), lh = (int)std::nearbyint(h * scale);
-    const size_t ln = (size_t)lw * lh;
-    float* flow = k == 0 ? flow_out : (prev_flow == fa ? fb : fa);
-    if (!prev_flow) {
-      const hipError_t e0 = hipMemsetAsync(flow, 0, ln * 2 * sizeof(float), st);
-      if (e0 != hipSuccess) return e0;
-    } else {
-      hipError_t e = launch_resize_lin(prev_flow, 1, ph, pw, 2, lh, lw, (float)(1. / pyr_scale), flow, st);
-      if (e != hipSuccess) return e;
-    }
-    // both images: to float, GaussianBlur(ksz, sigma), resize to the level, polynomial expansion
-    hipLaunchKernelGGL(u8_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, prev, n, img);
-    hipLaunchKernelGGL(u8_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, next, n, img + n);
-    hipError_t e = launch_gauss(img, 2, h, w, ksz, sigma, tmp, st);
-    if (e != hipSuccess) return e;
-    const float* lev = img;
-    if (lw != w || lh != h) {
-      e = launch_resize_lin(img, 2, h, w, 1, lh, lw, 1.f, I, st);
-      if (e != hipSuccess) return e;
-      lev = I;
-    }
-    const dim3 gl((unsigned)((ln + 255) / 256), 1, 2);
-    hipLaunchKernelGGL(polyexp_v_kernel, gl, dim3(256), 0, st, lev, lh, lw, pt, row3);
-    hipLaunchKernelGGL(polyexp_h_kernel, gl, dim3(256), 0, st, row3, lh, lw, pt, R);
-    const dim3 g1((unsigned)((ln + 255) / 256));
-    hipLaunchKernelGGL(update_matrices_kernel, g1, dim3(256), 0, st, R, R + 5 * ln, flow, lh, lw, M);
-    const dim3 gv((unsigned)((lw + 255) / 256), (unsigned)((lh + BOX_ROWS - 1) / BOX_ROWS));
-    const dim3 gh((unsigned)((lw + 255) / 256), (unsigned)lh);
-    const size_t hl = (size_t)(256 + 2 * m) * 5 * sizeof(double);
-    for (int it = 0; it < iterations; ++it) {
-      hipLaunchKernelGGL(box_v_kernel, gv, dim3(256), 0, st, M, lh, lw, m, vs);
-      hipLaunchKernelGGL(box_h_solve_kernel, gh, dim3(256), hl, st, vs, lh, lw, m, bscale, flow);
-      if (it < iterations - 1)
-        hipLaunchKernelGGL(update_matrices_kernel, g1, dim3(256), 0, st, R, R + 5 * ln, flow, lh, lw, M);
-    }
-    prev_flow = flow;
-    pw = lw;
-    ph = lh;
-  }
-  return hipGetLastError();
 }
 
 // ---- cv2.resize(src, (ow, oh), interpolation=INTER_AREA) of u8 images (--flow_downscale's grays,
@@ -569,24 +328,18 @@ hipError_t launch_motion_alpha(const float* flow, int h, int w, float norm, doub
   hipLaunchKernelGGL(motion_mag_kernel, g, dim3(256), 0, st, flow, hw, norm, alpha);
   // cv2.GaussianBlur(m, (0, 0), sigma) on float: ksize = cvRound(sigma * 4 * 2 + 1) | 1
   const int ksz = ((int)std::nearbyint(sigma * 8 + 1)) | 1;
-  hipError_t e = launch_gauss(alpha, 1, h, w, ksz, sigma, tmp, st);
+  hipError_t e = gauss_blur(alpha, 1, h, w, ksz, sigma, tmp, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(motion_alpha_kernel, g, dim3(256), 0, st, alpha, hw, max_alpha, span);
   return hipGetLastError();
 }
 
-void gaussian_taps_f32(int n, double sigma, float* t) {
-  const Taps tp = gaussian_taps(n, sigma);
-  for (int i = 0; i < n; ++i) t[i] = tp.t[i];
-}
-
-// ---- Farneback for n pairs in the same launches (nst_flow_farneback_ex; the morph's forward and backward flows
-// are n = 2 with the images swapped).  The image planes are [prev_0 .. prev_n-1, next_0 .. next_n-1], so that the
-// blur, the resize and PolyExp above take them as 2n planes; the three kernels below are the single-pair
-// UpdateMatrices and box kernels with the pair in blockIdx.z (same arithmetic, same order: n = 1 is bit-identical to
-// launch_farneback). ----
-__global__ __launch_bounds__(256) void update_matrices_n_kernel(const float* __restrict__ R, const float* __restrict__ flow_n,
-                                                                int n, int h, int w, float* __restrict__ M_n) {
+// ---- Farneback for n pairs in the same launches (nst_flow_farneback is n = 1; the morph's forward and backward
+// flows are n = 2 with the images swapped).  The image planes are [prev_0 .. prev_n-1, next_0 .. next_n-1], so that
+// the blur, the resize and PolyExp above take them as 2n planes; the kernels below take the pair from blockIdx.z. ----
+// FarnebackUpdateMatrices
+__global__ __launch_bounds__(256) void update_matrices_kernel(const float* __restrict__ R, const float* __restrict__ flow_n,
+                                                              int n, int h, int w, float* __restrict__ M_n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   const size_t hw = (size_t)h * w;
   if (i >= hw) return;
@@ -640,8 +393,15 @@ __global__ __launch_bounds__(256) void update_matrices_n_kernel(const float* __r
   m[4] = r6 * r2 + r5 * r3;
 }
 
-__global__ __launch_bounds__(256) void box_v_n_kernel(const float* __restrict__ M_n, int h, int w, int m,
-                                                      double* __restrict__ vs_n) {
+// FarnebackUpdateFlow_Blur: block_size x block_size box sums of M (rows and columns clamped to the frame)
+// in double, then the 2x2 solve with the 1e-3 regulariser.  As OpenCV sums them: a running vertical sum per
+// column (each step adds the float difference entering - leaving row), then the horizontal window over the
+// vertical sums.  Vertical: one thread per column walks a strip of BOX_ROWS rows; horizontal: a 256-pixel row
+// segment and its halo staged in LDS.
+constexpr int BOX_ROWS = 16;
+
+__global__ __launch_bounds__(256) void box_v_kernel(const float* __restrict__ M_n, int h, int w, int m,
+                                                    double* __restrict__ vs_n) {
   const int x = blockIdx.x * 256 + threadIdx.x;
   if (x >= w) return;
   const float* M = M_n + (size_t)blockIdx.z * h * w * 5;
@@ -667,8 +427,8 @@ __global__ __launch_bounds__(256) void box_v_n_kernel(const float* __restrict__ 
   }
 }
 
-__global__ __launch_bounds__(256) void box_h_solve_n_kernel(const double* __restrict__ vs_n, int h, int w, int m,
-                                                            double scale, float* __restrict__ flow_n) {
+__global__ __launch_bounds__(256) void box_h_solve_kernel(const double* __restrict__ vs_n, int h, int w, int m,
+                                                          double scale, float* __restrict__ flow_n) {
   extern __shared__ double seg[];  // (256 + 2m) x 5
   const double* vs = vs_n + (size_t)blockIdx.z * h * w * 5;
   float* flow = flow_n + (size_t)blockIdx.z * h * w * 2;
@@ -777,59 +537,6 @@ __global__ __launch_bounds__(256) void gwin_h_solve_kernel(const float* __restri
   flow[2 * i + 1] = (g22 * h1 - g12 * h2) * idet;
 }
 
-// The pyramid's pre-blur grows with the depth (ksize = round(5 sigma) | 1, sigma = (1 / scale - 1) / 2): the morph's 5
-// and 6 levels reach 77 taps at 1080p, past launch_gauss's 63.  Same kernels with a table of up to 511 taps (the
-// same accumulation order), used for the levels that need it.
-constexpr int WIDE_TAPS = 511;
-struct WideTaps {
-  int n;
-  float t[WIDE_TAPS];
-};
-
-__global__ __launch_bounds__(256) void gauss_rows_wide_kernel(const float* __restrict__ in, int h, int w, WideTaps tp,
-                                                              float* __restrict__ out) {
-  const size_t plane = (size_t)blockIdx.z * h * w;
-  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
-  const int r = tp.n / 2;
-  const float* row = in + plane + (size_t)y * w;
-  float acc = 0.f;
-  for (int j = 0; j < tp.n; ++j) acc = acc + tp.t[j] * row[refl101(x + j - r, w)];
-  out[plane + (size_t)y * w + x] = acc;
-}
-
-__global__ __launch_bounds__(256) void gauss_cols_wide_kernel(const float* __restrict__ in, int h, int w, WideTaps tp,
-                                                              float* __restrict__ out) {
-  const size_t plane = (size_t)blockIdx.z * h * w;
-  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
-  const int r = tp.n / 2;
-  float acc = 0.f;
-  for (int j = 0; j < tp.n; ++j) acc = acc + tp.t[j] * in[plane + (size_t)refl101(y + j - r, h) * w + x];
-  out[plane + (size_t)y * w + x] = acc;
-}
-
-static hipError_t launch_gauss_wide(float* planes, int k, int h, int w, int ksize, double sigma, float* tmp,
-                                    hipStream_t st) {
-  if (ksize <= 63) return launch_gauss(planes, k, h, w, ksize, sigma, tmp, st);
-  if (ksize > WIDE_TAPS) return hipErrorInvalidValue;
-  WideTaps tp;  // cv2.getGaussianKernel(ksize, sigma > 0, CV_32F), as gaussian_taps
-  tp.n = ksize;
-  const double s2 = -0.5 / (sigma * sigma);
-  double sum = 0;
-  double v[WIDE_TAPS];
-  for (int i = 0; i < ksize; ++i) {
-    const double x = i - (ksize - 1) * 0.5;
-    v[i] = std::exp(s2 * x * x);
-    sum += v[i];
-  }
-  for (int i = 0; i < WIDE_TAPS; ++i) tp.t[i] = i < ksize ? (float)(v[i] / sum) : 0.f;
-  const dim3 g((unsigned)((w + 255) / 256), (unsigned)h, (unsigned)k);
-  hipLaunchKernelGGL(gauss_rows_wide_kernel, g, dim3(256), 0, st, planes, h, w, tp, tmp);
-  hipLaunchKernelGGL(gauss_cols_wide_kernel, g, dim3(256), 0, st, tmp, h, w, tp, planes);
-  return hipGetLastError();
-}
-
 // the widest pre-blur of the pyramid launch_farneback_ex would run (its level rule), for the entry point's check
 int farneback_max_ksize(int h, int w, double pyr_scale, int levels) {
   int k;
@@ -845,7 +552,8 @@ int farneback_max_ksize(int h, int w, double pyr_scale, int levels) {
 }
 
 size_t farneback_scratch_floats_ex(int n, int h, int w) {
-  // per pair what farneback_scratch_floats counts (the + 64 covers the padding before the 8-byte-aligned window sums)
+  // per pair: img f32 x2, tmp x2, I x2, row3 x2 (3ch), R x2 (5ch), M (5ch), vs (5 doubles = 10 floats), flow x2
+  // (2ch); the + 64 covers the padding before the 8-byte-aligned window sums
   return (size_t)n * h * w * (2 + 2 + 2 + 6 + 10 + 5 + 10 + 4) + 64;
 }
 
@@ -896,7 +604,7 @@ hipError_t launch_farneback_ex(const uint8_t* prev, const uint8_t* next, int np,
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(u8_to_f32_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, prev, N, img);
     hipLaunchKernelGGL(u8_to_f32_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, next, N, img + N);
-    e = launch_gauss_wide(img, 2 * np, h, w, ksz, sigma, tmp, st);
+    e = gauss_blur(img, 2 * np, h, w, ksz, sigma, tmp, st);
     if (e != hipSuccess) return e;
     const float* lev = img;
     if (lw != w || lh != h) {
@@ -908,7 +616,7 @@ hipError_t launch_farneback_ex(const uint8_t* prev, const uint8_t* next, int np,
     hipLaunchKernelGGL(polyexp_v_kernel, gl, dim3(256), 0, st, lev, lh, lw, pt, row3);
     hipLaunchKernelGGL(polyexp_h_kernel, gl, dim3(256), 0, st, row3, lh, lw, pt, R);
     const dim3 g1((unsigned)((ln + 255) / 256), 1, (unsigned)np);
-    hipLaunchKernelGGL(update_matrices_n_kernel, g1, dim3(256), 0, st, R, flow, np, lh, lw, M);
+    hipLaunchKernelGGL(update_matrices_kernel, g1, dim3(256), 0, st, R, flow, np, lh, lw, M);
     const dim3 gv((unsigned)((lw + 255) / 256), (unsigned)((lh + BOX_ROWS - 1) / BOX_ROWS), (unsigned)np);
     const dim3 gh((unsigned)((lw + 255) / 256), (unsigned)lh, (unsigned)np);
     const size_t hl = (size_t)(256 + 2 * m) * 5 * (gaussian ? sizeof(float) : sizeof(double));
@@ -917,10 +625,10 @@ hipError_t launch_farneback_ex(const uint8_t* prev, const uint8_t* next, int np,
         hipLaunchKernelGGL(gwin_v_kernel, g1, dim3(256), 0, st, M, lh, lw, wt, (float*)vs);
         hipLaunchKernelGGL(gwin_h_solve_kernel, gh, dim3(256), hl, st, (const float*)vs, lh, lw, wt, flow);
       } else {
-        hipLaunchKernelGGL(box_v_n_kernel, gv, dim3(256), 0, st, M, lh, lw, m, vs);
-        hipLaunchKernelGGL(box_h_solve_n_kernel, gh, dim3(256), hl, st, vs, lh, lw, m, bscale, flow);
+        hipLaunchKernelGGL(box_v_kernel, gv, dim3(256), 0, st, M, lh, lw, m, vs);
+        hipLaunchKernelGGL(box_h_solve_kernel, gh, dim3(256), hl, st, vs, lh, lw, m, bscale, flow);
       }
-      if (it < iterations - 1) hipLaunchKernelGGL(update_matrices_n_kernel, g1, dim3(256), 0, st, R, flow, np, lh, lw, M);
+      if (it < iterations - 1) hipLaunchKernelGGL(update_matrices_kernel, g1, dim3(256), 0, st, R, flow, np, lh, lw, M);
     }
     prev_flow = flow;
     pw = lw;

@@ -11,6 +11,8 @@
 // translation unit is built with -ffp-contract=off: every fp32 product and sum rounds on its own, in the order written.
 #include <math.h>
 
+#include "blur_internal.h"
+#include "border_common.h"
 #include "flow_internal.h"
 
 namespace nst {
@@ -27,12 +29,6 @@ hipError_t launch_gray_cv(const uint8_t* rgb, size_t npix, uint8_t* gray, hipStr
   return hipGetLastError();
 }
 
-__device__ __forceinline__ int refl101_m(int p, int n) {
-  if (n == 1) return 0;
-  while (p < 0 || p >= n) p = p < 0 ? -p : 2 * n - 2 - p;
-  return p;
-}
-
 struct Taps5 {
   float t[5];
 };
@@ -41,7 +37,7 @@ struct Taps15 {
 };
 
 // cv2.GaussianBlur(u8, (5, 5), 1.0) as the float path would do it: the rows' 5-tap sums (BORDER_REFLECT_101), then
-// the columns' over those, each acc = acc + t[j] * v in tap order as gauss_rows_kernel / gauss_cols_kernel, then
+// the columns' over those, each acc = acc + t[j] * v in tap order as blur_rows_kernel / blur_cols_kernel, then
 // rounded half-to-even to u8.  One thread per output pixel recomputes the 5 row sums it needs (the same values a
 // row pass would have stored).  OpenCV >= 4 blurs 8-bit images in 8.8 fixed point instead, so cv2's own result may
 // differ from this one by 1 grey level; that difference is unmeasured (cv2 absent).
@@ -54,11 +50,11 @@ __global__ __launch_bounds__(256) void gauss_u8_kernel(const uint8_t* __restrict
   const int x = (int)(i % w), y = (int)(i / w);
   int xs[5];
 #pragma unroll
-  for (int j = 0; j < 5; ++j) xs[j] = refl101_m(x + j - 2, w);
+  for (int j = 0; j < 5; ++j) xs[j] = border_reflect101(x + j - 2, w);
   float acc = 0.f;
 #pragma unroll
   for (int r = 0; r < 5; ++r) {
-    const uint8_t* row = src + (size_t)refl101_m(y + r - 2, h) * w;
+    const uint8_t* row = src + (size_t)border_reflect101(y + r - 2, h) * w;
     float ra = 0.f;
 #pragma unroll
     for (int j = 0; j < 5; ++j) ra = ra + tp.t[j] * (float)row[xs[j]];
@@ -77,7 +73,7 @@ hipError_t launch_gauss_u8(const uint8_t* in, int n, int h, int w, uint8_t* out,
 }
 
 // ---- morph_v2.py:405-432: blur both flow components 15 x 15 (sigma 3, REFLECT_101; rows then columns, the
-// accumulation order of gauss_rows_kernel / gauss_cols_kernel), then add the radial term where the blurred flow
+// accumulation order of blur_rows_kernel / blur_cols_kernel), then add the radial term where the blurred flow
 // is shorter than 2 px.  numpy adds the float64 term to the float32 flow and rounds once. ----
 __global__ __launch_bounds__(256) void flow_blur_rows_kernel(const float2* __restrict__ in, int h, int w, Taps15 tp,
                                                              float2* __restrict__ out) {
@@ -89,7 +85,7 @@ __global__ __launch_bounds__(256) void flow_blur_rows_kernel(const float2* __res
   float ax = 0.f, ay = 0.f;
 #pragma unroll
   for (int j = 0; j < 15; ++j) {
-    const float2 v = row[refl101_m(x + j - 7, w)];
+    const float2 v = row[border_reflect101(x + j - 7, w)];
     ax = ax + tp.t[j] * v.x;
     ay = ay + tp.t[j] * v.y;
   }
@@ -110,7 +106,7 @@ __global__ __launch_bounds__(256) void flow_blur_cols_radial_kernel(const float2
   float dx = 0.f, dy = 0.f;
 #pragma unroll
   for (int j = 0; j < 15; ++j) {
-    const float2 v = pl[(size_t)refl101_m(y + j - 7, h) * w + x];
+    const float2 v = pl[(size_t)border_reflect101(y + j - 7, h) * w + x];
     dx = dx + tp.t[j] * v.x;
     dy = dy + tp.t[j] * v.y;
   }
@@ -142,14 +138,6 @@ struct MorphSched {
   float t[128], omt[128], wa[128], wb[128];  // NST_MORPH_MAX_FRAMES
 };
 
-// BORDER_REFLECT (fedcba|abcdefgh|hgfedcba) of any integer position
-__device__ __forceinline__ int reflect_idx(int p, int n) {
-  const int n2 = 2 * n;
-  int r = p % n2;
-  if (r < 0) r += n2;
-  return r < n ? r : n2 - 1 - r;
-}
-
 // cv2.remap(INTER_LINEAR, BORDER_REFLECT) of one u8 RGB pixel at the fp32 map position (mx, my): the position is
 // clamped far outside the frame first (NaN to the low end; cv2's saturate_cast<int>(map * 32) saturates), which
 // keeps the int conversion defined and reflects to the same sample; then 5 fraction bits, the four taps reflected
@@ -159,8 +147,8 @@ __device__ __forceinline__ void remap_reflect(const uint8_t* __restrict__ img, i
   my = fminf(fmaxf(my, -2.f * h), 3.f * h);
   const int X = (int)rintf(mx * 32.f), Y = (int)rintf(my * 32.f);
   const int sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31;
-  const int x0 = reflect_idx(sx, w), x1 = reflect_idx(sx + 1, w);
-  const int y0 = reflect_idx(sy, h), y1 = reflect_idx(sy + 1, h);
+  const int x0 = border_reflect(sx, w), x1 = border_reflect(sx + 1, w);
+  const int y0 = border_reflect(sy, h), y1 = border_reflect(sy + 1, h);
   const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
   const uint8_t* p00 = img + ((size_t)y0 * w + x0) * 3;
   const uint8_t* p01 = img + ((size_t)y0 * w + x1) * 3;

@@ -9,6 +9,7 @@
 #include "seg_internal.h"
 #include "nst_hip.h"
 #include "post_common.h"
+#include "border_common.h"
 #include "conv_impl.h"
 
 namespace nst {
@@ -878,11 +879,6 @@ hipError_t launch_lab_blend(const uint32_t* rgb2lab, const uint32_t* lab2rgb, co
 // alpha = m / 255 (pipeline.py:353).  cv2 is not importable here: parity unpinned (OpenCV's 8-bit
 // path quantises the taps to fixed point, which can move a rounding boundary by 1 LSB).
 constexpr int FEATHER_MAX_R = 1023;
-__device__ __forceinline__ int reflect101(int i, int n) {
-  if (n == 1) return 0;
-  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
-  return i;
-}
 __device__ void feather_taps(float* k, int r, double sigma) {
   __shared__ double part[256];
   double s = 0.0;
@@ -911,7 +907,7 @@ __global__ __launch_bounds__(256) void feather_rows_kernel(const uint8_t* __rest
   const size_t f = (size_t)blockIdx.z * h * w;
   if (x >= w) return;
   float s = 0.f;
-  for (int i = -r; i <= r; ++i) s += k[i + r] * (float)m[f + (size_t)y * w + reflect101(x + i, w)];
+  for (int i = -r; i <= r; ++i) s += k[i + r] * (float)m[f + (size_t)y * w + border_reflect101(x + i, w)];
   tmp[f + (size_t)y * w + x] = s;
 }
 __global__ __launch_bounds__(256) void feather_cols_kernel(const float* __restrict__ tmp, int h, int w, int r,
@@ -923,7 +919,7 @@ __global__ __launch_bounds__(256) void feather_cols_kernel(const float* __restri
   const size_t f = (size_t)blockIdx.z * h * w;
   if (x >= w) return;
   float s = 0.f;
-  for (int i = -r; i <= r; ++i) s += k[i + r] * tmp[f + (size_t)reflect101(y + i, h) * w + x];
+  for (int i = -r; i <= r; ++i) s += k[i + r] * tmp[f + (size_t)border_reflect101(y + i, h) * w + x];
   const float u8 = fminf(fmaxf(rintf(s), 0.f), 255.f);  // saturate_cast<uchar>
   if (out_u8) out_u8[f + (size_t)y * w + x] = (uint8_t)u8;  // the blurred mask itself (sky_swap.py:213-215)
   else alpha[f + (size_t)y * w + x] = u8 / 255.0f;

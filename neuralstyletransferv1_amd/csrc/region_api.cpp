@@ -3,6 +3,7 @@
 
 #include <string>
 
+#include "blur_internal.h"
 #include "nst_hip.h"
 #include "nst_internal.h"
 #include "region_internal.h"
@@ -82,9 +83,12 @@ int nst_region_masks(int kind, int count, int n_gen, const int* ivals, const dou
   return NST_OK;
 }
 
+// feather_mask (region_blend.py:69-102): F.pad(reflect) + conv2d with the outer product of the 1-D Gaussian taps,
+// computed as a row pass then a column pass by the shared blur (the taps are the host's fp32 copies of the
+// reference's torch taps)
 int nst_region_feather(float* masks, int k, int h, int w, const float* taps, int ks, float* scratch, void* stream) {
-  if (!masks || !taps || !scratch || k <= 0 || h <= 0 || w <= 0 || ks < 1 || ks > RG_MAX_TAPS || (ks & 1) == 0) {
-    set_error("nst_region_feather: invalid arguments (odd ks <= " + std::to_string(RG_MAX_TAPS) + ")");
+  if (!masks || !taps || !scratch || k <= 0 || h <= 0 || w <= 0 || ks < 1 || ks > BLUR_MAX_TAPS || (ks & 1) == 0) {
+    set_error("nst_region_feather: invalid arguments (odd ks <= " + std::to_string(BLUR_MAX_TAPS) + ")");
     return NST_E_INVALID;
   }
   if (ks / 2 >= h || ks / 2 >= w) {  // F.pad(mode='reflect') needs pad < dim (torch raises too)
@@ -92,7 +96,7 @@ int nst_region_feather(float* masks, int k, int h, int w, const float* taps, int
               std::to_string(h) + "x" + std::to_string(w));
     return NST_E_SHAPE;
   }
-  RG_LAUNCH(launch_region_feather(masks, k, h, w, taps, ks, scratch, (hipStream_t)stream), "region_feather");
+  RG_LAUNCH(launch_sep_blur_f32(masks, k, h, w, taps, ks, scratch, (hipStream_t)stream), "region_feather");
   return NST_OK;
 }
 

@@ -12,7 +12,6 @@ namespace nst {
 constexpr int RG_MAX = 32;        // regions per composite (NST_REGION_MAX)
 constexpr int RG_TERMS = 9;       // models A..H + the original per region
 constexpr int RG_MAX_SRC = 16;    // model outputs (x scales) per composite
-constexpr int RG_MAX_TAPS = 511;  // Gaussian feather taps (feather <= 255 px)
 
 // geometry of one generate_region_masks call, fp32 constants already rounded as torch rounds them
 struct RegionGeomDev {
@@ -48,8 +47,6 @@ struct RegionSrcSet {
 static_assert(sizeof(RegionSrcSet) + sizeof(RegionTermsDev) <= 3600, "region tables exceed the kernarg budget");
 
 hipError_t launch_region_masks(const RegionGeomDev& g, int h, int w, float* masks, float* scratch, hipStream_t st);
-hipError_t launch_region_feather(float* masks, int k, int h, int w, const float* taps, int ks, float* scratch,
-                                 hipStream_t st);
 hipError_t launch_region_rotate(const float* in, int k, int h, int w, const double* M, float* out, hipStream_t st);
 hipError_t launch_region_bbox(const float* masks, int k, int h, int w, float thr, int* bbox, hipStream_t st);
 hipError_t launch_region_composite(const RegionSrcSet& ss, const RegionTermsDev& t, const uint8_t* orig,

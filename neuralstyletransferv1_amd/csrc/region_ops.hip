@@ -15,6 +15,7 @@
 // truncation (pipeline.py:1943) is fused into the store.
 #include <math.h>
 
+#include "border_common.h"
 #include "region_internal.h"
 
 namespace nst {
@@ -174,62 +175,6 @@ hipError_t launch_region_masks(const RegionGeomDev& g, int h, int w, float* mask
   }
   hipLaunchKernelGGL(region_masks_kernel, dim3((unsigned)((hw + 255) / 256)), dim3(256), 0, st, g, h, w, pos, mm,
                      masks);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------
-// feather_mask (region_blend.py:69-102): F.pad(reflect) + conv2d with the outer product of the 1-D
-// Gaussian taps, computed here as a row pass then a column pass (the taps are the host's fp32 copies of
-// the reference's torch taps).  Row tiles of 256 pixels + halo staged in LDS.
-struct FeatherTaps {
-  int ks;
-  float t[RG_MAX_TAPS];
-};
-
-__device__ __forceinline__ int reflect101(int p, int n) {
-  p = p < 0 ? -p : p;
-  return p >= n ? 2 * n - 2 - p : p;
-}
-
-__global__ __launch_bounds__(256) void feather_row_kernel(const float* __restrict__ in, int h, int w, FeatherTaps tp,
-                                                          float* __restrict__ out) {
-  extern __shared__ float row[];  // 256 + ks - 1 entries
-  const int pad = tp.ks / 2;
-  const size_t plane = (size_t)blockIdx.z * h * w;
-  const int y = blockIdx.y, x0 = blockIdx.x * 256;
-  const float* src = in + plane + (size_t)y * w;
-  for (int j = threadIdx.x; j < 256 + tp.ks - 1; j += 256) {
-    const int xs = x0 + j - pad;
-    row[j] = (xs < w + pad) ? src[reflect101(xs, w)] : 0.f;
-  }
-  __syncthreads();
-  const int x = x0 + threadIdx.x;
-  if (x >= w) return;
-  float acc = 0.f;
-  for (int j = 0; j < tp.ks; ++j) acc = acc + tp.t[j] * row[threadIdx.x + j];
-  out[plane + (size_t)y * w + x] = acc;
-}
-
-__global__ __launch_bounds__(256) void feather_col_kernel(const float* __restrict__ in, int h, int w, FeatherTaps tp,
-                                                          float* __restrict__ out) {
-  const int pad = tp.ks / 2;
-  const size_t plane = (size_t)blockIdx.z * h * w;
-  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
-  float acc = 0.f;
-  for (int i = 0; i < tp.ks; ++i) acc = acc + tp.t[i] * in[plane + (size_t)reflect101(y + i - pad, h) * w + x];
-  out[plane + (size_t)y * w + x] = acc;
-}
-
-hipError_t launch_region_feather(float* masks, int k, int h, int w, const float* taps, int ks, float* scratch,
-                                 hipStream_t st) {
-  FeatherTaps tp;
-  tp.ks = ks;
-  for (int i = 0; i < ks; ++i) tp.t[i] = taps[i];
-  const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h, (unsigned)k);
-  hipLaunchKernelGGL(feather_row_kernel, grid, dim3(256), (256 + ks - 1) * sizeof(float), st, masks, h, w, tp,
-                     scratch);
-  hipLaunchKernelGGL(feather_col_kernel, grid, dim3(256), 0, st, scratch, h, w, tp, masks);
   return hipGetLastError();
 }
 
@@ -668,19 +613,13 @@ __global__ __launch_bounds__(256) void morph_minmax_kernel(const float2* __restr
   if (threadIdx.x == 0) mm[kf] = make_float2(smin[0], smax[0]);
 }
 
-__device__ __forceinline__ int reflect_cv(int p, int n) {  // cv2 BORDER_REFLECT: fedcba|abcdefgh|hgfedcb
-  if (n == 1) return 0;
-  while (p < 0 || p >= n) p = p < 0 ? -p - 1 : 2 * n - p - 1;
-  return p;
-}
-
 // cv2.remap(src, map_x, map_y, INTER_LINEAR, BORDER_REFLECT) at one pixel
 __device__ __forceinline__ float remap_reflect(const float* src, int h, int w, float mx, float my) {
   const int X = (int)rintf(mx * 32.f), Y = (int)rintf(my * 32.f);
   const int sx = X >> 5, sy = Y >> 5;
   const float fx = (float)(X & 31) * (1.f / 32.f), fy = (float)(Y & 31) * (1.f / 32.f);
   const float w00 = (1.f - fy) * (1.f - fx), w01 = (1.f - fy) * fx, w10 = fy * (1.f - fx), w11 = fy * fx;
-  const int x0 = reflect_cv(sx, w), x1 = reflect_cv(sx + 1, w), y0 = reflect_cv(sy, h), y1 = reflect_cv(sy + 1, h);
+  const int x0 = border_reflect(sx, w), x1 = border_reflect(sx + 1, w), y0 = border_reflect(sy, h), y1 = border_reflect(sy + 1, h);
   const float t0 = src[(size_t)y0 * w + x0] * w00 + src[(size_t)y0 * w + x1] * w01;
   const float t1 = src[(size_t)y1 * w + x0] * w10 + src[(size_t)y1 * w + x1] * w11;
   return t0 + t1;

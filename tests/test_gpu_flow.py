@@ -10,7 +10,15 @@ translation recovered within 0.15 px (the restatement's own accuracy at finest s
 
 Bars: luma bit-exact vs Pillow; Farneback flow within 2e-3 px of the restatement on >= 99.9 % of pixels (the
 same fp32/fp64 operation order; the host exp() of the taps and libm differences can move a fraction of an ulp
-through 4 pyramid levels x 3 iterations), translation recovered within 0.05 px; fuse / motion alpha 2e-6."""
+through 4 pyramid levels x 3 iterations), translation recovered within 0.05 px; fuse / motion alpha 2e-6.
+
+The Farneback flow and the motion alpha are also pinned bit for bit to what the library gave before the two Farneback
+implementations and the four separable blurs became one each (tests/golden/flow_blur_parent.npz, recorded by
+tests/golden/make_golden_flow_blur.py from the parent commit): no tolerance."""
+import functools
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -21,8 +29,38 @@ from neuralstyletransferv1_amd import synthetic, temporal as T
 from oracle import flow_oracle as FO
 from oracle import nst_oracle as NO
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import make_golden_flow_blur as MG  # noqa: E402  (the seeded inputs of the recorded cases)
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
+
+
+@functools.lru_cache(maxsize=None)
+def _parent():
+    return np.load(MG.FIXTURE)
+
+
+def _assert_parent_bits(got, key):
+    ref = _parent()[key]
+    assert got.dtype == np.float32 and got.shape == ref.shape, (key, got.dtype, got.shape)
+    same = got.view(np.uint32) == ref.view(np.uint32)
+    assert same.all(), f"{key}: {int((~same).sum())} of {same.size} values differ from the parent commit's bits"
+
+
+@pytest.mark.parametrize("hw", MG.FARNEBACK_SIZES)
+def test_farneback_bits_equal_parent_commit(hw):
+    """72x96: one pyramid level survives (resize path, first matrix update from zero flow); 33x47: none, only the
+    3-tap sigma <= 0 pre-blur, odd sizes, the 5-pixel border-scale bands nearly meet."""
+    _assert_parent_bits(MG.gpu_farneback(*hw), f"farneback_{hw[0]}x{hw[1]}")
+
+
+def test_motion_alpha_bits_equal_parent_commit():
+    """Sigma 3 on a 10x12 flow: the blur's half-width 12 >= both sizes, so border indices reflect twice (what a
+    single-reflection helper gets wrong).  No comparison with FO.motion_alpha here: the oracle's _refl101 reflects
+    once (at w = 12 it maps position 23 to -1, which numpy wraps to the far end), so it does not model this size."""
+    assert int(FO._refl101(np.array([23]), 12)[0]) == -1
+    _assert_parent_bits(MG.gpu_motion_alpha(), "motion_alpha")
 
 
 def _pair(h, w, dx, dy, seed=0):
@@ -51,6 +89,14 @@ def test_farneback_vs_restatement(hw):
     assert (d > 2e-3).mean() <= 1e-3, float(d.max())
     c = got[20:-20, 20:-20]
     assert abs(float(np.median(c[..., 0])) - 3) < 0.05 and abs(float(np.median(c[..., 1])) + 2) < 0.05
+
+
+def test_farneback_refuses_a_pyramid_deeper_than_the_tap_table():
+    """The same check as nst_flow_farneback_ex, before any launch or use of the pointers: 20000x20000 at 9 levels
+    would need a pre-blur wider than 511 taps."""
+    from neuralstyletransferv1_amd import _lib
+    rc = _lib.lib().nst_flow_farneback(1, 1, 20000, 20000, 0.5, 9, 15, 3, 5, 1.1, 1, 1, 10 ** 15, None)
+    assert rc == _lib.NST_E_SHAPE
 
 
 def test_farneback_1080p_translation():

@@ -3,8 +3,10 @@ neuralstyletransferv1_amd/morph.py) against the numpy restatement tests/morph_re
 cv2 is not installed here: parity with OpenCV itself is unpinned for every test below; the yardstick is the
 restatement, which tests/test_morph_host.py pins to closed forms and properties.
 
-Bars: the box path of nst_flow_farneback_ex is bit-identical to nst_flow_farneback; grey, pre-blur and every morph
-frame byte-exact (integer weights, fp32 products and sums without contraction: nothing to tolerate); the flow
+Bars: the box path of nst_flow_farneback_ex is bit-identical to nst_flow_farneback (the same code since the two
+Farneback implementations became one, so at n = 1 that compares the code with itself: what pins those bits is
+test_gpu_flow.test_farneback_bits_equal_parent_commit; at n = 2 it still says that a pair in a batch equals the pair
+alone); grey, pre-blur and every morph frame byte-exact (integer weights, fp32 products and sums without contraction: nothing to tolerate); the flow
 post-processing within 1e-5 * max(1, |v|) away from the 2-px threshold; the Gaussian-window flow see
 test_gaussian_flow_vs_restatement."""
 import ctypes
@@ -80,9 +82,10 @@ def test_gaussian_flow_vs_restatement(hw, preset):
 
 
 def test_gaussian_flow_deep_pyramid_wide_pre_blur():
-    """A pyramid whose coarsest level needs more than 63 pre-blur taps (the 1080p presets need 77) takes the wide
-    table: 896x900 at pyr_scale 0.19 / 2 levels blurs with round(5 * 13.35) | 1 = 67 taps (the smallest frame that
-    reaches it: the coarsest level must keep 32 pixels), 2 iterations to keep the numpy side short.  Same bar."""
+    """A pyramid whose coarsest level needs a wide pre-blur (the 1080p presets need 77 taps; every size runs the one
+    blur with its 511-tap table): 896x900 at pyr_scale 0.19 / 2 levels blurs with round(5 * 13.35) | 1 = 67 taps (the
+    smallest frame that passes 63: the coarsest level must keep 32 pixels), 2 iterations to keep the numpy side
+    short.  Same bar."""
     par = (0.19, 2, 15, 2, 5, 1.1)
     assert MR.surviving_levels(896, 900, 2, 0.19) == 2
     prev, nxt = MR.texture_pair(896, 900, 3, -2)

@@ -6,9 +6,12 @@ concentric); the atan2/sin patterns (radial, spiral, waves) may flip a pixel sit
 vs torch's SLEEF, <= 0.05 % of pixels).  Feathered masks 2e-6 absolute (separable vs 2-D conv rounding).
 Composites 2e-6 absolute in fp32, uint8 within 1 LSB of the truncated fp32 reference.  Rotation is checked
 against the oracle's restatement of cv2.warpAffine only (cv2 absent: parity unpinned).
+nst_region_feather is also pinned bit for bit to what it gave before it moved to the blur it shares with the
+temporal stage (tests/golden/flow_blur_parent.npz, recorded from the parent commit): no tolerance.
 """
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -19,7 +22,10 @@ from oracle import region_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+sys.path.insert(0, GOLD)
+import make_golden_flow_blur as MG  # noqa: E402  (the seeded inputs of the recorded cases)
+
 G = np.load(os.path.join(GOLD, "regions.npz"))
 with open(os.path.join(GOLD, "regions.json")) as f:
     META = json.load(f)
@@ -55,6 +61,17 @@ def test_weighted_voronoi_and_feathers_vs_reference():
         assert np.abs(m.numpy() - G[f"fmasks_{mode}"]).max() <= 2e-6, mode
     _, m = gpu_masks("grid", 4, 1, 20)
     assert np.abs(m.numpy() - G["fmasks_grid_f20"]).max() <= 2e-6
+
+
+@pytest.mark.parametrize("name", sorted(MG.FEATHER_CASES))
+def test_feather_bits_equal_parent_commit(name):
+    """nst_region_feather on seeded random planes: 4 x 45x80 with ks = 81 (half-width 40, the widest the entry point
+    admits at that height), 2 x 12x300 with ks = 21 (two 256-pixel row tiles, the second partial: the LDS halo across
+    the tile edge, for every user of the shared row kernel)."""
+    got, ref = MG.gpu_feather(name), np.load(MG.FIXTURE)[name]
+    assert got.dtype == np.float32 and got.shape == ref.shape
+    same = got.view(np.uint32) == ref.view(np.uint32)
+    assert same.all(), f"{name}: {int((~same).sum())} of {same.size} values differ from the parent commit's bits"
 
 
 def _sources():
