@@ -9,7 +9,7 @@ BUILD := build/obj
 SLP ?= -fno-slp-vectorize
 CXXFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off $(SLP) -Wall -Wno-unused-function \
             -Iinclude -I$(CSRC)
-SRCS := $(CSRC)/conv_bf16.hip $(CSRC)/conv_f16.hip $(CSRC)/conv_bf16_wl.hip $(CSRC)/conv_wphase.hip $(CSRC)/conv_ws2.hip $(CSRC)/conv_ws9.hip $(CSRC)/conv_ws1s.hip $(CSRC)/conv_out9.hip $(CSRC)/conv_prep.hip $(CSRC)/conv_f32.hip $(CSRC)/conv_f32s.hip $(CSRC)/conv_vgg.hip $(CSRC)/nst_ops.hip $(CSRC)/t7_ops.hip $(CSRC)/vgg_ops.hip $(CSRC)/conv_gemm.hip $(CSRC)/seg_ops.hip $(CSRC)/seg_drn_head.hip $(CSRC)/region_ops.hip $(CSRC)/blur_ops.hip $(CSRC)/flow_ops.hip $(CSRC)/morph_ops.hip $(CSRC)/camera_ops.hip $(CSRC)/style_morph_ops.hip $(CSRC)/dis_ops.hip $(CSRC)/png_enc.hip $(CSRC)/jpeg_dec.hip $(CSRC)/jpeg_enc.hip $(CSRC)/nst_api.cpp $(CSRC)/vgg_gatys.cpp $(CSRC)/seg_deeplab.cpp $(CSRC)/region_api.cpp $(CSRC)/flow_api.cpp $(CSRC)/jpeg_entropy.cpp
+SRCS := $(CSRC)/conv_bf16.hip $(CSRC)/conv_f16.hip $(CSRC)/conv_bf16_wl.hip $(CSRC)/conv_wphase.hip $(CSRC)/conv_ws2.hip $(CSRC)/conv_ws9.hip $(CSRC)/conv_ws1s.hip $(CSRC)/conv_out9.hip $(CSRC)/conv_prep.hip $(CSRC)/conv_f32.hip $(CSRC)/conv_f32s.hip $(CSRC)/conv_vgg.hip $(CSRC)/nst_ops.hip $(CSRC)/t7_ops.hip $(CSRC)/vgg_ops.hip $(CSRC)/conv_gemm.hip $(CSRC)/seg_ops.hip $(CSRC)/seg_drn_head.hip $(CSRC)/region_ops.hip $(CSRC)/blur_ops.hip $(CSRC)/flow_ops.hip $(CSRC)/morph_ops.hip $(CSRC)/camera_ops.hip $(CSRC)/style_morph_ops.hip $(CSRC)/multi_model_ops.hip $(CSRC)/dis_ops.hip $(CSRC)/png_enc.hip $(CSRC)/jpeg_dec.hip $(CSRC)/jpeg_enc.hip $(CSRC)/nst_api.cpp $(CSRC)/vgg_gatys.cpp $(CSRC)/seg_deeplab.cpp $(CSRC)/region_api.cpp $(CSRC)/flow_api.cpp $(CSRC)/jpeg_entropy.cpp
 # conv_wst16.hip (the residual trunk): nine objects from one source (NST_W16_PART: 0..7 two explicitly instantiated
 # kernels each, ~2-3 min per kernel, compiled in parallel; 8 the launchers and the table)
 W16_OBJS := $(patsubst %,$(BUILD)/conv_wst16_p%.hip.o,0 1 2 3 4 5 6 7 8)
@@ -48,8 +48,9 @@ $(BUILD)/%.cpp.o: $(CSRC)/%.cpp $(CSRC)/nst_internal.h $(CSRC)/seg_internal.h $(
 
 # the JPEG reader's two halves share their record layout; the JPEG writer uses the same block geometry
 $(BUILD)/jpeg_dec.hip.o $(BUILD)/jpeg_enc.hip.o $(BUILD)/jpeg_entropy.cpp.o: $(CSRC)/jpeg_common.h
-# the camera's hue rotation and the style morph's saturation filters share cv2's 8-bit HSV conversions
-$(BUILD)/camera_ops.hip.o $(BUILD)/style_morph_ops.hip.o: $(CSRC)/hsv_common.h
+# the camera's hue rotation and the style morph's and multi-model video's saturation filters share cv2's 8-bit HSV
+# conversions
+$(BUILD)/camera_ops.hip.o $(BUILD)/style_morph_ops.hip.o $(BUILD)/multi_model_ops.hip.o: $(CSRC)/hsv_common.h
 # the blurs, the flows' gradients and warps and the mask feathers share OpenCV's two mirrored border rules
 $(BUILD)/blur_ops.hip.o $(BUILD)/dis_ops.hip.o $(BUILD)/morph_ops.hip.o $(BUILD)/nst_ops.hip.o $(BUILD)/region_ops.hip.o: $(CSRC)/border_common.h
 

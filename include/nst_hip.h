@@ -710,6 +710,56 @@ typedef struct nst_style_morph_frame {
 int nst_style_morph_frames(const uint8_t* bank, int n_bank, int h, int w, const nst_style_morph_frame* frames, int n,
                            uint8_t* out, void* stream);
 
+/* ---- Multi-model video: the pulsed multi-style compositor of scripts/multi_model_video.py
+ * (create_multi_model_video :239-353, get_styled_frame :60-107, adjust_saturation :113-122; multi_model_video.py
+ * here) ----
+ * n output frames [n,h,w,3] u8 RGB from a bank of u8 RGB images [n_bank,h,w,3] (device; image i at byte i*h*w*3, any
+ * alignment) and a host table of n descriptors; any n >= 1, the call splits it into launches itself.  One pass per
+ * frame, the running value in registers.  Per channel, in fp32 without contraction, each product and sum rounded
+ * alone; trunc(x) = (uint8)min(max(x, 0), 255), numpy's np.clip(x, 0, 255).astype(np.uint8).  In the script's order:
+ *   ST(s), a styled still (get_styled_frame), s = {orig, lo, hi, orig_w, style_w, w_lo, w_hi}:
+ *     lo < 0:  bank[orig] unchanged (the script's `return orig.astype(np.uint8)`)
+ *     else     sf = hi < 0 ? (float)bank[lo] : (float)bank[lo] * w_lo + (float)bank[hi] * w_hi
+ *              ST = trunc((float)bank[orig] * orig_w + sf * style_w)
+ *   base       B = base_kind == NST_MM_PLAIN ? bank[base.orig] : ST(base)
+ *   overlays   F = (float)B;  for k < n_over (0..2: mosaic, then tenharmsel):  F = F * keep[k] + (float)ST(over[k]) *
+ *              over_w[k]  (ST truncated to u8 before it enters the sum);  U = trunc(F)
+ *   saturation (adjust_saturation) when sat_on: 8-bit RGB2HSV (as nst_camera_hue_u8), s' = trunc((float)s * sat),
+ *              HSV2RGB: the arithmetic of NST_SM_FILTER_SAT
+ *   fades      G = (float)U
+ *              fin >= 0:  G = (float)bank[fin] * fin_w[0] + G * fin_w[1]                    (fade-in from the original)
+ *              cross_kind != NST_MM_NONE:  N = cross_kind == NST_MM_PLAIN ? bank[next.orig] : ST(next);
+ *                         G = G * cross_w[0] + (float)N * cross_w[1]     (no truncation between fade-in and cross-fade)
+ *   out = trunc(G)
+ * Every weight is a double the host rounds to fp32 once when it fills the struct.  The arithmetic is the reference's
+ * own numpy float32 code; only the two cvtColor calls are restated (parity unpinned, as the camera stage).
+ * NST_E_INVALID: n < 1, n_bank < 1, a null pointer, an index outside 0..n_bank-1 where it is read (lo < 0, hi < 0,
+ * fin < 0 are the absent forms; a plain image reads orig alone), n_over outside 0..2, an unknown base or cross kind,
+ * out overlapping the bank; NST_E_SHAPE: h or w outside 1..32768.  Everything is checked before the first launch. */
+#define NST_MM_NONE 0
+#define NST_MM_PLAIN 1
+#define NST_MM_STYLED 2
+typedef struct nst_multi_model_still {
+  int orig, lo, hi;
+  float orig_w, style_w, w_lo, w_hi;
+} nst_multi_model_still;
+typedef struct nst_multi_model_frame {
+  int base_kind; /* NST_MM_PLAIN or NST_MM_STYLED */
+  nst_multi_model_still base;
+  int n_over;
+  nst_multi_model_still over[2];
+  float keep[2], over_w[2];
+  int sat_on;
+  float sat;
+  int fin;
+  float fin_w[2];
+  int cross_kind; /* NST_MM_NONE, NST_MM_PLAIN or NST_MM_STYLED */
+  nst_multi_model_still next;
+  float cross_w[2];
+} nst_multi_model_frame;
+int nst_multi_model_frames(const uint8_t* bank, int n_bank, int h, int w, const nst_multi_model_frame* frames, int n,
+                           uint8_t* out, void* stream);
+
 /* ---- PNG encode on the owner rank (pipeline.py:2099-2119 `Image.fromarray(out).save(path)`, the reference's
  * default --image_ext png at :2170) ----
  * n u8 frames [n,h,w,c] (c = 1 grey, 3 RGB, 4 RGBA; device) -> n complete PNG files, file j at out + j*out_stride,

@@ -61,13 +61,14 @@ EXPORTED_SYMBOLS = (
     "nst_morph_frames",
     "nst_camera_pulse_u8", "nst_camera_rect_subpix_u8", "nst_camera_lanczos_u8", "nst_camera_hue_u8",
     "nst_camera_smooth_u8", "nst_camera_scratch_bytes", "nst_camera_frames_u8",
-    "nst_style_morph_frames",
+    "nst_style_morph_frames", "nst_multi_model_frames",
 )
 NST_FLOW_GAUSSIAN = 256  # cv2.OPTFLOW_FARNEBACK_GAUSSIAN (nst_flow_farneback_ex flags)
 NST_MORPH_MAX_FRAMES = 128  # frames per nst_morph_frames launch
 NST_CAMERA_MAX_FRAMES, NST_CAMERA_MAX_SMOOTH = 32, 15  # frames per nst_camera_* call, widest temporal kernel
 NST_STYLE_MORPH_MAX_STYLES = 8  # ladder families per side of an nst_style_morph_frames descriptor
 NST_SM_FILTER_NONE, NST_SM_FILTER_SAT, NST_SM_FILTER_VIBRANCE, NST_SM_FILTER_WARM = 0, 1, 2, 3
+NST_MM_NONE, NST_MM_PLAIN, NST_MM_STYLED = 0, 1, 2  # base / cross kinds of an nst_multi_model_frames descriptor
 NST_E_INVALID, NST_E_SHAPE, NST_E_WORKSPACE, NST_E_DATA = -1, -3, -5, -7
 NST_JPEG_444, NST_JPEG_422, NST_JPEG_420 = 0, 1, 2
 # region compositor limits / geometry kinds (include/nst_hip.h NST_REGION_*, NST_RG_*)
@@ -120,6 +121,22 @@ class NstStyleMorphFrame(ctypes.Structure):
     """nst_style_morph_frame: one output frame of the style morph (include/nst_hip.h "Style morph")."""
     _fields_ = [("n_sides", ctypes.c_int), ("fade", ctypes.c_float * 2), ("side", NstStyleMorphSide * 2),
                 ("filter", ctypes.c_int), ("fparam", ctypes.c_float * 3)]
+
+
+class NstMultiModelStill(ctypes.Structure):
+    """nst_multi_model_still: a styled still ST(s) -- the original, the two rungs (lo < 0: the original alone; hi < 0:
+    one rung) and their weights -- or, where the frame says plain, the image `orig`."""
+    _fields_ = [("orig", ctypes.c_int), ("lo", ctypes.c_int), ("hi", ctypes.c_int), ("orig_w", ctypes.c_float),
+                ("style_w", ctypes.c_float), ("w_lo", ctypes.c_float), ("w_hi", ctypes.c_float)]
+
+
+class NstMultiModelFrame(ctypes.Structure):
+    """nst_multi_model_frame: one output frame of the multi-model video (include/nst_hip.h "Multi-model video")."""
+    _fields_ = [("base_kind", ctypes.c_int), ("base", NstMultiModelStill), ("n_over", ctypes.c_int),
+                ("over", NstMultiModelStill * 2), ("keep", ctypes.c_float * 2), ("over_w", ctypes.c_float * 2),
+                ("sat_on", ctypes.c_int), ("sat", ctypes.c_float), ("fin", ctypes.c_int),
+                ("fin_w", ctypes.c_float * 2), ("cross_kind", ctypes.c_int), ("next", NstMultiModelStill),
+                ("cross_w", ctypes.c_float * 2)]
 
 
 _lib = None
@@ -301,6 +318,8 @@ def lib() -> ctypes.CDLL:
             getattr(L, name).restype = i
         L.nst_style_morph_frames.argtypes = [vp, i, i, i, ctypes.POINTER(NstStyleMorphFrame), i, vp, vp]
         L.nst_style_morph_frames.restype = i
+        L.nst_multi_model_frames.argtypes = [vp, i, i, i, ctypes.POINTER(NstMultiModelFrame), i, vp, vp]
+        L.nst_multi_model_frames.restype = i
         for name in ("nst_png_bound", "nst_png_workspace_bytes", "nst_png_encode_u8"):
             getattr(L, name).restype = i
         for name in ("nst_lab_planes_u8", "nst_lab_ema_planes", "nst_lab_merge_u8", "nst_input_exact"):

@@ -1,5 +1,6 @@
-// hsv_common.h — cv2.cvtColor's 8-bit RGB <-> HSV on one pixel, shared by camera_ops.hip (apply_hue_shift) and
-// style_morph_ops.hip (boost_saturation, vibrance).  Restated from OpenCV's sources (cv2 absent, parity unpinned);
+// hsv_common.h — cv2.cvtColor's 8-bit RGB <-> HSV on one pixel, shared by camera_ops.hip (apply_hue_shift),
+// style_morph_ops.hip (boost_saturation, vibrance) and multi_model_ops.hip (adjust_saturation).  Restated from
+// OpenCV's sources (cv2 absent, parity unpinned);
 // tests/camera_ref.py rgb_to_hsv8 / hsv8_to_rgb is the yardstick, byte for byte.  Include from translation units
 // built with -ffp-contract=off.
 #pragma once

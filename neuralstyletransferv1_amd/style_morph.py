@@ -18,8 +18,8 @@ yardstick.
 The script draws an unseeded random.choice(FILTERS) per image; here --filter fixes it or --seed (default 0) seeds
 random.Random(seed).choice, drawn once per loaded image in order.
 
-Out of scope (not built): multi_model_video.py, cv2's VideoWriter and the H.264 re-encode (assemble_video replaces
-them), the Magenta back end, face detection.
+Out of scope (not built): cv2's VideoWriter and the H.264 re-encode (assemble_video replaces them), the Magenta back
+end, face detection.  The stills' other consumer, multi_model_video.py, is its own module (multi_model_video.py here).
 """
 from __future__ import annotations
 
