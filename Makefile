@@ -51,6 +51,9 @@ $(BUILD)/jpeg_dec.hip.o $(BUILD)/jpeg_enc.hip.o $(BUILD)/jpeg_entropy.cpp.o: $(C
 # the camera's hue rotation and the style morph's and multi-model video's saturation filters share cv2's 8-bit HSV
 # conversions
 $(BUILD)/camera_ops.hip.o $(BUILD)/style_morph_ops.hip.o $(BUILD)/multi_model_ops.hip.o: $(CSRC)/hsv_common.h
+# the four u8 frame compositors and their entry points share the pixel run, its load and store, the shape refusal and
+# the bank-call frame
+$(BUILD)/morph_ops.hip.o $(BUILD)/camera_ops.hip.o $(BUILD)/style_morph_ops.hip.o $(BUILD)/multi_model_ops.hip.o $(BUILD)/flow_api.cpp.o build/asan/flow_api.cpp.o: $(CSRC)/u8run_common.h
 # the blurs, the flows' gradients and warps and the mask feathers share OpenCV's two mirrored border rules
 $(BUILD)/blur_ops.hip.o $(BUILD)/dis_ops.hip.o $(BUILD)/morph_ops.hip.o $(BUILD)/nst_ops.hip.o $(BUILD)/region_ops.hip.o: $(CSRC)/border_common.h
 

@@ -30,6 +30,7 @@ import torch
 
 from . import _lib
 from ._lib import NstCameraFrame, NstError, check, lib
+from .stills import ease_in_out_cubic
 
 PAN_DIRECTIONS = ("horizontal", "vertical", "diagonal", "diagonal_reverse")
 MAX_FRAMES = _lib.NST_CAMERA_MAX_FRAMES
@@ -48,10 +49,6 @@ class CameraFrame:
     cx: float         # getRectSubPix centre, double (the kernel takes it as float32, as cv2 does)
     cy: float
     hue_shift: float  # degrees; |shift| < 0.1 leaves the frame alone
-
-
-def ease_in_out_cubic(t: float) -> float:
-    return 4 * t * t * t if t < 0.5 else 1 - pow(-2 * t + 2, 3) / 2
 
 
 def calculate_zoom_pulse(progress: float, amplitude: float, frequency: float) -> float:

@@ -7,7 +7,8 @@
 //   (d) hue rotation   8-bit BGR2HSV (fixed point), fp32 remainder, HSV2BGR (float path);
 //   (e) temporal_smooth_frames with NumPy >= 2 promotion (double products, fp32 accumulator, double quotient);
 //   (f) the fused launch pair the CLI uses: zoom-phase patches go through scratch, pan-phase frames are one gather
-//       pass over the morph frame (pulse taps recomputed under the sub-pixel taps) and one store.
+//       pass over the morph frame (pulse taps recomputed under the sub-pixel taps) and one store, the run and its store
+//       from the compositor core (u8run_common.h).
 // cv2 is not installed here: all of it is restated from OpenCV's sources and the script, parity unpinned; the
 // yardstick is tests/camera_ref.py, byte for byte.  Built with -ffp-contract=off: every product and sum rounds alone.
 #include <hip/hip_runtime.h>
@@ -19,6 +20,7 @@
 #include "hsv_common.h"
 #include "nst_hip.h"
 #include "nst_internal.h"
+#include "u8run_common.h"
 
 namespace nst {
 namespace {
@@ -223,24 +225,20 @@ __global__ __launch_bounds__(256) void camera_crop_kernel(const uint8_t* __restr
   o[2] = (uint8_t)rgb[2];
 }
 
-// every frame's output: CAM_RUN consecutive pixels per thread; zoom phase = Lanczos of its patch, pan phase = the
-// sub-pixel gather from the morph frame; then the hue rotation.  VEC as nst_morph_frames: three dword stores when
-// every frame's run is 4-byte aligned.
-constexpr int CAM_RUN = 4;
-
+// every frame's output: one run of U8_RUN consecutive pixels per thread (u8run_common.h); zoom phase = Lanczos of its
+// patch, pan phase = the sub-pixel gather from the morph frame; then the hue rotation and store_run.
 template <bool VEC>
 __global__ __launch_bounds__(256) void camera_out_kernel(const uint8_t* __restrict__ in, int h, int w, CamBatch cb, int th,
                                                          int tw, LancTab tab, const uint8_t* __restrict__ scratch,
                                                          uint8_t* __restrict__ out) {
   const size_t opix = (size_t)th * tw;
-  const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * CAM_RUN;
+  const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * U8_RUN;
   if (i0 >= opix) return;
   const CamFrame& f = cb.f[blockIdx.z];
   const uint8_t* src = in + (size_t)blockIdx.z * h * w * 3;
-  const int cnt = (int)min((size_t)CAM_RUN, opix - i0);
-  uint32_t b[CAM_RUN * 3];
+  RunBytes rb;
 #pragma unroll
-  for (int j = 0; j < CAM_RUN; ++j) {
+  for (int j = 0; j < U8_RUN; ++j) {
     const size_t i = min(i0 + j, opix - 1);
     const int x = (int)(i % tw), y = (int)(i / tw);
     int rgb[3];
@@ -249,24 +247,11 @@ __global__ __launch_bounds__(256) void camera_out_kernel(const uint8_t* __restri
     else
       subpix_px(src, h, w, f, x, y, rgb);
     if (f.hue_on) hue_px(rgb, f.hue_half);
-    b[j * 3] = (uint32_t)rgb[0];
-    b[j * 3 + 1] = (uint32_t)rgb[1];
-    b[j * 3 + 2] = (uint32_t)rgb[2];
+    rb.b[j * 3] = (uint32_t)rgb[0];
+    rb.b[j * 3 + 1] = (uint32_t)rgb[1];
+    rb.b[j * 3 + 2] = (uint32_t)rgb[2];
   }
-  uint8_t* o = out + ((size_t)blockIdx.z * opix + i0) * 3;
-  if (VEC && cnt == CAM_RUN) {
-    uint32_t* o4 = (uint32_t*)o;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) o4[q] = b[4 * q] | (b[4 * q + 1] << 8) | (b[4 * q + 2] << 16) | (b[4 * q + 3] << 24);
-  } else {
-#pragma unroll
-    for (int j = 0; j < CAM_RUN; ++j)
-      if (j < cnt) {
-        o[j * 3] = (uint8_t)b[j * 3];
-        o[j * 3 + 1] = (uint8_t)b[j * 3 + 1];
-        o[j * 3 + 2] = (uint8_t)b[j * 3 + 2];
-      }
-  }
+  store_run<VEC>(out + ((size_t)blockIdx.z * opix + i0) * 3, rb, run_count<VEC>(i0, opix));
 }
 
 // ---- (e) ----
@@ -314,8 +299,7 @@ bool bad_dims(const char* who, int n, int h, int w, int* rc) {
     *rc = NST_E_INVALID;
     return true;
   }
-  if (h < 1 || w < 1 || h > 32768 || w > 32768) {
-    set_error(std::string(who) + ": frame " + std::to_string(w) + "x" + std::to_string(h) + " outside 1..32768");
+  if (bad_frame_shape(who, h, w)) {
     *rc = NST_E_SHAPE;
     return true;
   }
@@ -479,10 +463,7 @@ int nst_camera_smooth_u8(const uint8_t* window, int win_n, int h, int w, int fir
               std::to_string(NST_CAMERA_MAX_SMOOTH));
     return NST_E_INVALID;
   }
-  if (h < 1 || w < 1 || h > 32768 || w > 32768) {
-    set_error("nst_camera_smooth_u8: frame " + std::to_string(w) + "x" + std::to_string(h) + " outside 1..32768");
-    return NST_E_SHAPE;
-  }
+  if (bad_frame_shape("nst_camera_smooth_u8", h, w)) return NST_E_SHAPE;
   const bool plain = seq_len <= kernel_size;  // the call site's condition: such a sequence is returned unchanged
   const int half = kernel_size / 2;
   const int lo = plain ? out_first : (out_first - half < 0 ? 0 : out_first - half);
@@ -598,10 +579,10 @@ int nst_camera_frames_u8(const uint8_t* in, int n, int h, int w, const nst_camer
   const size_t opix = (size_t)th * tw;
   const bool vec = (opix % 4) == 0 && ((uintptr_t)out & 3) == 0;
   if (vec)
-    hipLaunchKernelGGL(camera_out_kernel<true>, px_grid(opix, CAM_RUN, n), dim3(256), 0, st, in, h, w, cb, th, tw, tab,
+    hipLaunchKernelGGL(camera_out_kernel<true>, px_grid(opix, U8_RUN, n), dim3(256), 0, st, in, h, w, cb, th, tw, tab,
                        (const uint8_t*)scratch, out);
   else
-    hipLaunchKernelGGL(camera_out_kernel<false>, px_grid(opix, CAM_RUN, n), dim3(256), 0, st, in, h, w, cb, th, tw, tab,
+    hipLaunchKernelGGL(camera_out_kernel<false>, px_grid(opix, U8_RUN, n), dim3(256), 0, st, in, h, w, cb, th, tw, tab,
                        (const uint8_t*)scratch, out);
   CAM_LAUNCHED("camera_out");
   return NST_OK;

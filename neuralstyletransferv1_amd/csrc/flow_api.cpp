@@ -5,6 +5,7 @@
 #include "flow_internal.h"
 #include "nst_hip.h"
 #include "nst_internal.h"
+#include "u8run_common.h"
 
 using namespace nst;
 
@@ -203,10 +204,7 @@ int nst_morph_frames(const uint8_t* img1, const uint8_t* img2, const float* flow
               ", flows 8-byte aligned)");
     return NST_E_INVALID;
   }
-  if (h < 1 || w < 1 || h > 32768 || w > 32768) {
-    set_error("nst_morph_frames: frame " + std::to_string(w) + "x" + std::to_string(h) + " outside 1..32768");
-    return NST_E_SHAPE;
-  }
+  if (bad_frame_shape("nst_morph_frames", h, w)) return NST_E_SHAPE;
   FL_LAUNCH(launch_morph_frames(img1, img2, flow_fwd, flow_bwd, h, w, k, t, one_minus_t, wa, wb, out,
                                 (hipStream_t)stream),
             "morph_frames");

@@ -6,7 +6,8 @@
 //   * morph_v2's flow post-processing: GaussianBlur((15, 15), 3.0) of each component, then the radial term where
 //     the blurred flow is shorter than 2 px;
 //   * every frame of a transition in one launch: two cv2.remap(INTER_LINEAR, BORDER_REFLECT) warps in OpenCV's
-//     1/32-pixel fixed point and cv2.addWeighted, per pixel over all k frames.
+//     1/32-pixel fixed point and cv2.addWeighted, per pixel over all k frames; the run of pixels a thread owns and its
+//     store are the compositor core's (u8run_common.h).
 // cv2 is not installed here: all of it is restated from OpenCV's sources and the scripts, parity unpinned.  The
 // translation unit is built with -ffp-contract=off: every fp32 product and sum rounds on its own, in the order written.
 #include <math.h>
@@ -14,6 +15,7 @@
 #include "blur_internal.h"
 #include "border_common.h"
 #include "flow_internal.h"
+#include "u8run_common.h"
 
 namespace nst {
 
@@ -165,24 +167,23 @@ __device__ __forceinline__ uint32_t add_weighted(int p1, int p2, float wa, float
   return (uint32_t)fminf(fmaxf(rintf(v), 0.f), 255.f);
 }
 
-// Each thread owns MORPH_RUN consecutive pixels (of the flattened frame), loads their forward and backward flow
+// Each thread owns one run of U8_RUN consecutive pixels (u8run_common.h), loads their forward and backward flow
 // vectors once and loops over the k frames: the 16 B of flow per pixel are read once per transition, not once per
-// frame.  VEC: the run's 12 output bytes leave as three dword stores (every frame's run is 4-byte aligned: h*w a
-// multiple of 4 and `out` aligned); otherwise, and for the tail, byte stores.
-constexpr int MORPH_RUN = 4;
-
+// frame.  Every frame's 12 output bytes leave through store_run.  The run's pixel count stays the computed one under
+// VEC too (run_count<false>): with it folded to the constant the compiler schedules the gathers differently and the
+// kernel measured 5 to 25 % slower (profiles/compositor_core_ab.txt).
 template <bool VEC>
 __global__ __launch_bounds__(256) void morph_frames_kernel(const uint8_t* __restrict__ img1, const uint8_t* __restrict__ img2,
                                                            const float2* __restrict__ fwd, const float2* __restrict__ bwd,
                                                            int h, int w, MorphSched sc, uint8_t* __restrict__ out) {
   const size_t hw = (size_t)h * w;
-  const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * MORPH_RUN;
+  const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * U8_RUN;
   if (i0 >= hw) return;
-  const int cnt = (int)min((size_t)MORPH_RUN, hw - i0);
-  float2 ff[MORPH_RUN], fb[MORPH_RUN];
-  float px[MORPH_RUN], py[MORPH_RUN];
+  const int cnt = run_count<false>(i0, hw);
+  float2 ff[U8_RUN], fb[U8_RUN];
+  float px[U8_RUN], py[U8_RUN];
 #pragma unroll
-  for (int j = 0; j < MORPH_RUN; ++j) {
+  for (int j = 0; j < U8_RUN; ++j) {
     const size_t i = min(i0 + j, hw - 1);
     ff[j] = fwd[i];
     fb[j] = bwd[i];
@@ -191,30 +192,16 @@ __global__ __launch_bounds__(256) void morph_frames_kernel(const uint8_t* __rest
   }
   for (int f = 0; f < sc.k; ++f) {
     const float t = sc.t[f], omt = sc.omt[f], wa = sc.wa[f], wb = sc.wb[f];
-    uint32_t b[MORPH_RUN * 3];
+    RunBytes rb;
 #pragma unroll
-    for (int j = 0; j < MORPH_RUN; ++j) {
+    for (int j = 0; j < U8_RUN; ++j) {
       int a[3], c[3];
       remap_reflect(img1, h, w, px[j] + t * ff[j].x, py[j] + t * ff[j].y, a);
       remap_reflect(img2, h, w, px[j] + omt * fb[j].x, py[j] + omt * fb[j].y, c);
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) b[j * 3 + ch] = add_weighted(a[ch], c[ch], wa, wb);
+      for (int ch = 0; ch < 3; ++ch) rb.b[j * 3 + ch] = add_weighted(a[ch], c[ch], wa, wb);
     }
-    uint8_t* o = out + ((size_t)f * hw + i0) * 3;
-    if (VEC && cnt == MORPH_RUN) {
-      uint32_t* o4 = (uint32_t*)o;
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-        o4[q] = b[4 * q] | (b[4 * q + 1] << 8) | (b[4 * q + 2] << 16) | (b[4 * q + 3] << 24);
-    } else {
-#pragma unroll
-      for (int j = 0; j < MORPH_RUN; ++j)
-        if (j < cnt) {
-          o[j * 3] = (uint8_t)b[j * 3];
-          o[j * 3 + 1] = (uint8_t)b[j * 3 + 1];
-          o[j * 3 + 2] = (uint8_t)b[j * 3 + 2];
-        }
-    }
+    store_run<VEC>(out + ((size_t)f * hw + i0) * 3, rb, cnt);
   }
 }
 
@@ -231,7 +218,7 @@ hipError_t launch_morph_frames(const uint8_t* img1, const uint8_t* img2, const f
     sc.wb[f] = in ? wb[f] : 0.f;
   }
   const size_t hw = (size_t)h * w;
-  const size_t threads = (hw + MORPH_RUN - 1) / MORPH_RUN;
+  const size_t threads = (hw + U8_RUN - 1) / U8_RUN;
   const dim3 g((unsigned)((threads + 255) / 256));
   const bool vec = (hw % 4) == 0 && ((uintptr_t)out & 3) == 0;
   if (vec)

@@ -47,8 +47,9 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, stills
 from ._lib import NstError, check, lib
+from .stills import FrameWriter, ease_in_out_cubic, smoothstep
 
 # pyr_scale, levels, winsize, iterations, poly_n, poly_sigma
 PRESETS = {
@@ -58,14 +59,6 @@ PRESETS = {
 EASINGS = ("linear", "smooth", "smoother")
 IMAGE_PATTERNS = ("*.jpg", "*.jpeg", "*.png")
 PAN_DIRECTIONS = ("horizontal", "vertical", "diagonal", "diagonal_reverse")
-
-
-def ease_in_out_cubic(t: float) -> float:
-    return 4 * t * t * t if t < 0.5 else 1 - pow(-2 * t + 2, 3) / 2
-
-
-def smoothstep(t: float) -> float:
-    return t * t * (3 - 2 * t)
 
 
 def smootherstep(t: float) -> float:
@@ -252,12 +245,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--easing", choices=EASINGS, default="smooth", help="warp timing of preset v2")
     ap.add_argument("--hold_frames", type=int, default=0, help="frames each still is shown before its transition")
     ap.add_argument("--hold_end", type=int, default=24, help="extra frames of the last still")
-    ap.add_argument("--output_dir", type=str, required=True)
-    ap.add_argument("--output_prefix", type=str, default="morph_frame")
-    ap.add_argument("--image_ext", choices=["png", "jpg"], default="png")
-    ap.add_argument("--jpeg_quality", type=int, default=85)
-    ap.add_argument("--png_writer", choices=["fast", "pil", "gpu"], default="pil")
-    ap.add_argument("--jpeg_writer", choices=["pil", "gpu"], default="pil")
+    stills.add_output_flags(ap, "morph_frame")
     ap.add_argument("--output_video", type=str, default=None, help="also assemble the frames with ffmpeg")
     ap.add_argument("--batch", type=int, default=24, help="frames per nst_morph_frames launch (and per write)")
     ap.add_argument("--device", type=str, default="cuda:0")
@@ -329,38 +317,6 @@ def load_fitted(path: Path, tw: int, th: int, device: torch.device) -> torch.Ten
     return x[0, sy:sy + th, sx:sx + tw].contiguous()
 
 
-class FrameWriter:
-    """Numbered files {prefix}_{0001..}.{ext} through the frame loop's writers."""
-
-    def __init__(self, out_dir: Path, prefix: str, ext: str, quality: int, png_writer: str, jpeg_writer: str):
-        self.dir, self.prefix, self.ext, self.quality = out_dir, prefix, ext, int(quality)
-        self.png_writer, self.jpeg_writer = png_writer, jpeg_writer
-        self.count = 0
-
-    def write(self, frames_u8: torch.Tensor) -> None:
-        from PIL import Image
-        blobs = None
-        if self.ext == "jpg" and self.jpeg_writer == "gpu":
-            from .jpegio import jpeg_bytes_gpu
-            blobs = jpeg_bytes_gpu(frames_u8, self.quality)
-        elif self.ext == "png" and self.png_writer == "gpu":
-            from .pngio import png_bytes_gpu
-            blobs = png_bytes_gpu(frames_u8)
-        host = None if blobs is not None else frames_u8.cpu().numpy()
-        for j in range(frames_u8.shape[0]):
-            self.count += 1
-            path = self.dir / f"{self.prefix}_{self.count:04d}.{self.ext}"
-            if blobs is not None:
-                path.write_bytes(blobs[j])
-            elif self.ext == "jpg":
-                Image.fromarray(host[j]).save(path, format="JPEG", quality=self.quality)
-            elif self.png_writer == "fast":
-                from .pngio import write_png
-                write_png(path, host[j])
-            else:
-                Image.fromarray(host[j]).save(path)
-
-
 def _hold(wr: FrameWriter, img: torch.Tensor, n: int, step: int) -> None:
     for s in range(0, n, step):
         wr.write(img[None].repeat(min(step, n - s), 1, 1, 1))
@@ -372,9 +328,7 @@ def _main_camera(args, files: Sequence[Path], k: int, size: Tuple[int, int]) -> 
     device = torch.device(args.device)
     tw, th = args.size
     zoom = args.zoom if args.zoom is not None else 1.0
-    out_dir = Path(args.output_dir)
-    out_dir.mkdir(parents=True, exist_ok=True)
-    wr = FrameWriter(out_dir, args.output_prefix, args.image_ext, args.jpeg_quality, args.png_writer, args.jpeg_writer)
+    wr = stills.open_writer(args)
     total = total_frames(len(files), k, args.hold_frames, args.hold_end)
     plan = CAM.frame_plan(total, size, (tw, th), args.pan_zoom, args.pan_direction or "horizontal",
                           0.25 if args.zoom_in_pct is None else args.zoom_in_pct, args.zoom_pulse,
@@ -408,10 +362,7 @@ def _main_camera(args, files: Sequence[Path], k: int, size: Tuple[int, int]) -> 
         print(f"[morph] {idx + 1}/{len(files)} {files[idx].name}: {g} frames")
     hold(cur, args.hold_end)
     assert g == total and wr.count == total
-    if args.output_video:
-        from .pipeline import assemble_video
-        assemble_video(out_dir, Path(args.output_video), args.fps, None, args.output_prefix)
-    print(f"[morph] wrote {wr.count} frames to {out_dir}")
+    stills.close_run("morph", wr, args.fps, args.output_video)
     return 0
 
 
@@ -435,9 +386,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         return _main_camera(args, files, k, size)
     device = torch.device(args.device)
     tw, th = args.size
-    out_dir = Path(args.output_dir)
-    out_dir.mkdir(parents=True, exist_ok=True)
-    wr = FrameWriter(out_dir, args.output_prefix, args.image_ext, args.jpeg_quality, args.png_writer, args.jpeg_writer)
+    wr = stills.open_writer(args)
     t, alpha = schedule(k, args.preset, args.easing)
     step = max(1, min(args.batch, _lib.NST_MORPH_MAX_FRAMES))
     cur = load_fitted(files[0], tw, th, device)
@@ -452,10 +401,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         print(f"[morph] {idx + 1}/{len(files)} {files[idx].name}: {wr.count} frames")
     _hold(wr, cur, args.hold_end, step)
     assert wr.count == total_frames(len(files), k, args.hold_frames, args.hold_end)
-    if args.output_video:
-        from .pipeline import assemble_video
-        assemble_video(out_dir, Path(args.output_video), args.fps, None, args.output_prefix)
-    print(f"[morph] wrote {wr.count} frames to {out_dir}")
+    stills.close_run("morph", wr, args.fps, args.output_video)
     return 0
 
 

@@ -30,17 +30,15 @@ import argparse
 import json
 import math
 import sys
-from concurrent.futures import ThreadPoolExecutor
 from datetime import datetime
 from pathlib import Path
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
-import numpy as np
 import torch
 
-from . import _lib
-from ._lib import NstError, check, lib
-from .style_morph import UsageError
+from . import _lib, stills
+from ._lib import NstError
+from .stills import UsageError, header_size, smoothstep
 
 STYLES = ("udnie", "mosaic", "tenharmsel")
 MOSAIC_DEFAULT = ("mosaic_style5e10",)  # the script's ladder for a mosaic directory without a walk file
@@ -56,10 +54,6 @@ def fitted_size(w: int, h: int, size: int = 1080, portrait: bool = True) -> Tupl
         return size, int(h * (size / w))
     scale = size / w if w > h else size / h
     return int(w * scale), int(h * scale)
-
-
-def smoothstep(t: float) -> float:
-    return t * t * (3 - 2 * t)
 
 
 def gaussian_pulse(t: float, num_pulses: int = 4, width: float = 0.15) -> float:
@@ -276,74 +270,24 @@ def pack(descs: Sequence[dict]):
 
 def multi_model_frames(bank_u8: torch.Tensor, descs: Sequence[dict]) -> torch.Tensor:
     """bank uint8 [n_bank,h,w,3] on the device, descriptors as plan() emits them -> uint8 [n,h,w,3]."""
-    _lib.require_gpu_tensor(bank_u8, "multi_model_frames bank")
-    if bank_u8.dtype != torch.uint8 or bank_u8.dim() != 4 or bank_u8.shape[3] != 3:
-        raise NstError(f"multi_model_frames: expected a uint8 [n_bank,h,w,3] bank, got {bank_u8.dtype} {tuple(bank_u8.shape)}")
-    bank = bank_u8.contiguous()
-    n_bank, h, w, _ = bank.shape
-    n = len(descs)
-    out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=bank.device)
-    check(lib().nst_multi_model_frames(bank.data_ptr(), n_bank, h, w, pack(descs), n, out.data_ptr(),
-                                       _lib.stream_ptr(bank.device)), "nst_multi_model_frames")
-    bank.record_stream(torch.cuda.current_stream(bank.device))
-    return out
+    return stills.bank_frames("multi_model_frames", "nst_multi_model_frames", pack, bank_u8, descs)
 
 
-def _decode_pil(path) -> np.ndarray:
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.array(im.convert("RGB"), dtype=np.uint8)
+def fit_rule(size: int, portrait: bool) -> stills.FitRule:
+    """The script's load_resize as stills.load_bank takes it: the whole image, scaled to fitted_size."""
+    def fit(w: int, h: int):
+        wh = fitted_size(w, h, size, portrait)
+        if wh[0] < 1 or wh[1] < 1:
+            raise NstError(f"a {w}x{h} image fits to {wh[0]}x{wh[1]}")
+        return None, wh
+    return fit
 
 
 def load_bank(paths: Sequence, size: int = 1080, portrait: bool = True, device=None,
               jpeg_reader: str = "pil") -> torch.Tensor:
-    """The script's load_resize over a list of files whose fitted sizes agree: uint8 [len(paths),h,w,3] on the device.
-    Pillow decodes to RGB (for cv2.imread) on a thread pool, or, jpeg_reader "gpu", jpegio.decode_gpu per geometry
-    with Pillow for the files off its fast path; cv2.resize(INTER_LANCZOS4) is camera.lanczos_resize, one call per
-    source geometry; a source already at the target size is copied."""
-    from .camera import lanczos_resize
-    device = torch.device(device or "cuda:0")
-    n = len(paths)
-    if n == 0:
-        raise NstError("load_bank: no files")
-    decoded: List[Optional[torch.Tensor]] = [None] * n  # uint8 [h,w,3] on the device
-    todo = list(range(n))
-    with ThreadPoolExecutor(max_workers=min(16, n)) as pool:
-        if jpeg_reader == "gpu":
-            from . import jpegio
-            blobs = list(pool.map(lambda p: Path(p).read_bytes(), paths))
-            groups: Dict[tuple, List[int]] = {}
-            for i, b in enumerate(blobs):
-                info = jpegio.probe(b)
-                if info is not None:
-                    groups.setdefault(info, []).append(i)
-            for idx in groups.values():
-                try:
-                    frames = jpegio.decode_gpu([blobs[i] for i in idx], device)
-                except NstError:  # a damaged stream among them: Pillow decides, file by file
-                    continue
-                for i, fr in zip(idx, frames):
-                    decoded[i] = fr
-            todo = [i for i in todo if decoded[i] is None]
-        for i, rgb in zip(todo, pool.map(_decode_pil, [paths[i] for i in todo])):
-            decoded[i] = torch.from_numpy(rgb).to(device)
-    target = None
-    by_geometry: Dict[Tuple[int, int], List[int]] = {}
-    for i, t in enumerate(decoded):
-        h, w = t.shape[:2]
-        wh = fitted_size(w, h, size, portrait)
-        if wh[0] < 1 or wh[1] < 1:
-            raise NstError(f"{paths[i]}: a {w}x{h} image fits to {wh[0]}x{wh[1]}")
-        if target is None:
-            target = wh
-        elif wh != target:
-            raise NstError(f"{paths[i]}: loads at {wh[0]}x{wh[1]}, {paths[0]} at {target[0]}x{target[1]}")
-        by_geometry.setdefault((w, h), []).append(i)
-    bank = torch.empty((n, target[1], target[0], 3), dtype=torch.uint8, device=device)
-    for (w, h), idx in by_geometry.items():
-        src = torch.stack([decoded[i] for i in idx])
-        bank[idx] = src if (w, h) == target else lanczos_resize(src, [(w, h)] * len(idx), target)
-    return bank
+    """The script's load_resize over a list of files whose fitted sizes agree (stills.load_bank under fit_rule): uint8
+    [len(paths),h,w,3] on the device; jpeg_reader "gpu" decodes the JPEGs on the device."""
+    return stills.load_bank(paths, fit_rule(size, portrait), device, jpeg_reader)
 
 
 def load_resize(path, size: int = 1080, portrait: bool = True, device=None) -> torch.Tensor:
@@ -370,25 +314,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--crossfade_seconds", type=float, default=2.0)
     ap.add_argument("--hold_frames", type=int, default=3, help="output frames per source frame")
     ap.add_argument("--saturation", type=float, default=1.3, help="saturation boost of styled frames (1.0: none)")
-    ap.add_argument("--output_dir", type=str, required=True)
-    ap.add_argument("--output_prefix", type=str, default="multi_model_frame")
-    ap.add_argument("--image_ext", choices=["png", "jpg"], default="png")
-    ap.add_argument("--jpeg_quality", type=int, default=85)
-    ap.add_argument("--png_writer", choices=["fast", "pil", "gpu"], default="pil")
-    ap.add_argument("--jpeg_writer", choices=["pil", "gpu"], default="pil")
+    stills.add_output_flags(ap, "multi_model_frame")
     ap.add_argument("--jpeg_reader", choices=["pil", "gpu"], default="pil")
     ap.add_argument("--batch", type=int, default=8, help="source frames per kernel call")
     ap.add_argument("--device", type=str, default="cuda:0")
     return ap
-
-
-def _header_size(path: Path) -> Optional[Tuple[int, int]]:
-    from PIL import Image
-    try:
-        with Image.open(path) as im:
-            return im.size
-    except Exception:  # cv2.imread returns None for a file it cannot read; the script then takes its None branch
-        return None
 
 
 def styled_dirs_of(args) -> Dict[str, str]:
@@ -418,7 +348,7 @@ def prepare(args) -> Tuple[List[dict], Tuple[int, int]]:
 
     def header(p: Path) -> Optional[Tuple[int, int]]:
         if p not in sizes:
-            sizes[p] = _header_size(p) if p.exists() else None
+            sizes[p] = header_size(p) if p.exists() else None
         return sizes[p]
 
     wh = header(first)
@@ -470,11 +400,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     except UsageError as e:
         print(f"[multi_model_video] {e}", file=sys.stderr)
         return 2
-    from .morph import FrameWriter
     device = torch.device(args.device)
-    out_dir = Path(args.output_dir)
-    out_dir.mkdir(parents=True, exist_ok=True)
-    wr = FrameWriter(out_dir, args.output_prefix, args.image_ext, args.jpeg_quality, args.png_writer, args.jpeg_writer)
+    wr = stills.open_writer(args)
     print(f"[multi_model_video] {len(pl)} source frames at {tw}x{th}, {args.hold_frames} output frames each")
     for s in range(0, len(pl), args.batch):
         group = pl[s:s + args.batch]
@@ -486,11 +413,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         frames = multi_model_frames(bank, descs)
         holds = torch.tensor([fr["hold"] for fr in group], device=device)
         wr.write(frames.repeat_interleave(holds, dim=0))
+    stills.close_run("multi_model_video", wr, args.fps, args.output)
     if args.output:
-        from .pipeline import assemble_video
-        assemble_video(out_dir, Path(args.output), args.fps, None, args.output_prefix)
         save_run_log(Path(args.output), args, styled_dirs_of(args), wr.count)
-    print(f"[multi_model_video] wrote {wr.count} frames to {out_dir}")
     return 0
 
 

@@ -30,11 +30,11 @@ import sys
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
-import numpy as np
 import torch
 
-from . import _lib
-from ._lib import NstError, check, lib
+from . import _lib, stills as shared  # `stills` names the collected images in this module
+from ._lib import NstError
+from .stills import UsageError, header_size
 
 _WEIGHTS = ("1e9", "5e9", "1e10", "5e10", "1e11", "5e11", "1e12")
 _TENHARMSEL = tuple(f"{m}e{e}" for e in (9, 10, 11) for m in range(1, 10)) + ("1e12",)
@@ -57,10 +57,6 @@ FILTER_PARAMS = {
     "warm": (_lib.NST_SM_FILTER_WARM, (1 + 0.05, 1 + 0.05 * 0.3, 1 - 0.05 * 0.3)),
 }
 ORIGINAL = ("original", 0)  # a still's key of its unstyled image; a ladder image's key is (family, rung)
-
-
-class UsageError(Exception):
-    """A condition the CLI reports with exit status 2 before it touches the device."""
 
 
 # ---- discovery ----
@@ -89,15 +85,6 @@ def fitted_size(w: int, h: int, size: int, portrait: bool) -> Tuple[int, int]:
     return (int(w * (size / h)), size) if portrait else (size, size)
 
 
-def _header_size(path: Path) -> Optional[Tuple[int, int]]:
-    from PIL import Image
-    try:
-        with Image.open(path) as im:
-            return im.size
-    except Exception:  # cv2.imread returns None for a file it cannot read; the script then skips the image
-        return None
-
-
 def collect(styled_dir, names: Sequence[str], ladders: Dict[str, Tuple[str, ...]], size: int = 1080,
             portrait: bool = False, filter_name: str = "random", seed: int = 0) -> List[dict]:
     """The script's preload loop without the pixels: per usable name (an _original.jpg and at least one ladder image)
@@ -113,7 +100,7 @@ def collect(styled_dir, names: Sequence[str], ladders: Dict[str, Tuple[str, ...]
 
         def present(style: str) -> Optional[Path]:
             p = root / f"{name}_{style}.jpg"
-            wh = _header_size(p) if p.exists() else None
+            wh = header_size(p) if p.exists() else None
             if wh is None:
                 return None
             sizes[p] = fitted_size(wh[0], wh[1], size, portrait)
@@ -263,44 +250,24 @@ def pack(descs: Sequence[dict]):
 
 def style_morph_frames(bank_u8: torch.Tensor, descs: Sequence[dict]) -> torch.Tensor:
     """bank uint8 [n_bank,h,w,3] on the device, descriptors as plan() emits them -> uint8 [n,h,w,3]."""
-    _lib.require_gpu_tensor(bank_u8, "style_morph_frames bank")
-    if bank_u8.dtype != torch.uint8 or bank_u8.dim() != 4 or bank_u8.shape[3] != 3:
-        raise NstError(f"style_morph_frames: expected a uint8 [n_bank,h,w,3] bank, got {bank_u8.dtype} {tuple(bank_u8.shape)}")
-    bank = bank_u8.contiguous()
-    n_bank, h, w, _ = bank.shape
-    n = len(descs)
-    out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=bank.device)
-    check(lib().nst_style_morph_frames(bank.data_ptr(), n_bank, h, w, pack(descs), n, out.data_ptr(),
-                                       _lib.stream_ptr(bank.device)), "nst_style_morph_frames")
-    bank.record_stream(torch.cuda.current_stream(bank.device))
-    return out
+    return shared.bank_frames("style_morph_frames", "nst_style_morph_frames", pack, bank_u8, descs)
+
+
+def fit_rule(size: int, portrait: bool) -> shared.FitRule:
+    """The script's load_resize as stills.load_bank takes it: the square centre crop or, portrait, the whole image at
+    height `size`."""
+    def fit(w: int, h: int):
+        tw, th = fitted_size(w, h, size, portrait)
+        if tw < 1:
+            raise NstError(f"portrait width int({w} * {size} / {h}) is 0")
+        side = min(w, h)
+        return (None if portrait else ((w - side) // 2, (h - side) // 2, side, side)), (tw, th)
+    return fit
 
 
 def load_resize(path, size: int = 1080, portrait: bool = False, device=None) -> torch.Tensor:
-    """The script's load_resize: Pillow decode to RGB (for cv2.imread), the square centre crop or, portrait, the whole
-    image at height `size`, then cv2.resize(INTER_LANCZOS4) as camera.lanczos_resize restates it; a source already at
-    the target size is copied.  uint8 [h,w,3] on the device."""
-    from PIL import Image
-
-    from .camera import lanczos_resize
-    with Image.open(path) as im:
-        rgb = np.array(im.convert("RGB"), dtype=np.uint8)
-    h, w = rgb.shape[:2]
-    tw, th = fitted_size(w, h, size, portrait)
-    if tw < 1:
-        raise NstError(f"{path}: portrait width int({w} * {size} / {h}) is 0")
-    if not portrait:
-        if w > h:
-            x = (w - h) // 2
-            rgb = rgb[:, x:x + h]
-        elif h > w:
-            y = (h - w) // 2
-            rgb = rgb[y:y + w, :]
-    ch, cw = rgb.shape[:2]
-    t = torch.from_numpy(np.ascontiguousarray(rgb)).to(torch.device(device or "cuda:0"))
-    if (cw, ch) == (tw, th):
-        return t
-    return lanczos_resize(t[None], [(cw, ch)], (tw, th))[0]
+    """The script's load_resize of one file (stills.load_bank under fit_rule): uint8 [h,w,3] on the device."""
+    return shared.load_bank([path], fit_rule(size, portrait), device)[0]
 
 
 def still_images(still: dict) -> Dict[Tuple[str, int], Path]:
@@ -315,7 +282,7 @@ def still_images(still: dict) -> Dict[Tuple[str, int], Path]:
 def load_bank(still: dict, needs: Sequence[Tuple[str, int]], size: int, portrait: bool, device) -> torch.Tensor:
     """The images of `needs`, in that order: uint8 [len(needs),h,w,3] on the device."""
     paths = still_images(still)
-    return torch.stack([load_resize(paths[key], size, portrait, device) for key in needs])
+    return shared.load_bank([paths[key] for key in needs], fit_rule(size, portrait), device)
 
 
 # ---- CLI ----
@@ -332,12 +299,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--families", type=str, nargs="+", help=f"style families to use (of {', '.join(LADDERS)})")
     ap.add_argument("--filter", choices=("random",) + FILTERS, default="random", help="every image's colour filter")
     ap.add_argument("--seed", type=int, default=0, help="seed of --filter random")
-    ap.add_argument("--output_dir", type=str, required=True)
-    ap.add_argument("--output_prefix", type=str, default="style_morph_frame")
-    ap.add_argument("--image_ext", choices=["png", "jpg"], default="png")
-    ap.add_argument("--jpeg_quality", type=int, default=85)
-    ap.add_argument("--png_writer", choices=["fast", "pil", "gpu"], default="pil")
-    ap.add_argument("--jpeg_writer", choices=["pil", "gpu"], default="pil")
+    shared.add_output_flags(ap, "style_morph_frame")
     ap.add_argument("--output_video", "--output", dest="output_video", type=str, default=None,
                     help="also assemble the frames with ffmpeg")
     ap.add_argument("--batch", type=int, default=24, help="frames per kernel call (and per write)")
@@ -371,11 +333,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     except UsageError as e:
         print(f"[style_morph] {e}", file=sys.stderr)
         return 2
-    from .morph import FrameWriter
     device = torch.device(args.device)
-    out_dir = Path(args.output_dir)
-    out_dir.mkdir(parents=True, exist_ok=True)
-    wr = FrameWriter(out_dir, args.output_prefix, args.image_ext, args.jpeg_quality, args.png_writer, args.jpeg_writer)
+    wr = shared.open_writer(args)
     frames, needs = pl["frames"], pl["needs"]
     cur = load_bank(stills[0], needs[0], args.size, args.portrait, device)
     pos = 0
@@ -392,10 +351,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         cur = nxt
         print(f"[style_morph] {idx + 1}/{len(stills)} {st['name']} ({st['filter']}): {wr.count} frames")
     assert pos == len(frames) == wr.count
-    if args.output_video:
-        from .pipeline import assemble_video
-        assemble_video(out_dir, Path(args.output_video), args.fps, None, args.output_prefix)
-    print(f"[style_morph] wrote {wr.count} frames to {out_dir}")
+    shared.close_run("style_morph", wr, args.fps, args.output_video)
     return 0
 
 

@@ -263,3 +263,33 @@ def test_cli_end_to_end(tmp_path):
     assert [f.name for f in outs_gpu] == [f.name for f in outs]
     for a, b in zip(outs, outs_gpu):
         assert a.read_bytes() == b.read_bytes(), a.name
+
+
+@pytest.mark.parametrize("reader", ["pil", "gpu"])
+def test_load_bank_scatter(tmp_path, reader):
+    """load_bank over three source geometries interleaved (64x50, 48x37, 96x75, 64x50; the two 64x50 files differ), all
+    fitting to 48x37: one Lanczos call per geometry, scattered back into bank order.  Expected as test_load_resize
+    builds it; the GPU reader on the kind of file test_cli_end_to_end shows it byte-equal to Pillow on."""
+    paths, want = [], []
+    for i, (w, h, seed) in enumerate([(64, 50, 21), (48, 37, 22), (96, 75, 23), (64, 50, 24)]):
+        p = tmp_path / f"f{i}.jpg"
+        _save_jpeg(p, w, h, seed)
+        rgb = np.array(Image.open(p).convert("RGB"), dtype=np.uint8)
+        assert MM.fitted_size(w, h, 48) == (48, 37)
+        paths.append(p)
+        want.append(rgb if (w, h) == (48, 37) else CR.lanczos_resize(rgb, 48, 37))
+    assert not np.array_equal(want[0], want[3])
+    got = MM.load_bank(paths, 48, True, DEV, reader)
+    assert got.dtype == torch.uint8 and got.is_contiguous() and tuple(got.shape) == (4, 37, 48, 3)
+    assert np.array_equal(got.cpu().numpy(), np.stack(want))
+
+
+def test_wrapper_refuses_bank():
+    """The shared wrapper's messages carry this wrapper's name."""
+    good = _descriptors()[:1]
+    with pytest.raises(_lib.NstError, match=r"^multi_model_frames: expected a uint8 \[n_bank,h,w,3\] bank, got torch.float32"):
+        MM.multi_model_frames(torch.zeros((N_BANK, 4, 4, 3), dtype=torch.float32, device=DEV), good)
+    with pytest.raises(_lib.NstError, match=r"^multi_model_frames: expected a uint8 \[n_bank,h,w,3\] bank, got torch.uint8 \(4, 4, 3\)"):
+        MM.multi_model_frames(torch.zeros((4, 4, 3), dtype=torch.uint8, device=DEV), good)
+    with pytest.raises(_lib.NstError, match=r"^multi_model_frames: expected a uint8 \[n_bank,h,w,3\] bank"):
+        MM.multi_model_frames(torch.zeros((N_BANK, 4, 4, 4), dtype=torch.uint8, device=DEV), good)

@@ -246,3 +246,39 @@ def test_cli_end_to_end(tmp_path, mode):
     for i, f in enumerate(files):
         got = np.array(Image.open(f))
         assert got.shape == (48, 48, 3) and np.array_equal(got, want[i]), (i, int((got != want[i]).sum()))
+
+
+def test_load_bank_scatter(tmp_path):
+    """load_bank over three source geometries interleaved (80x60, 48x48, 50x70, 80x60; the two 80x60 files differ):
+    one Lanczos call per geometry, scattered back into bank order.  Expected as test_load_resize builds it."""
+    files = [("original", 80, 60, 11), ("candy", 48, 48, 12), ("candy_style1e9", 50, 70, 13), ("candy_style5e9", 80, 60, 14)]
+    want = []
+    for style, w, h, seed in files:
+        p = tmp_path / f"IMG_{style}.jpg"
+        _save_jpeg(p, w, h, seed)
+        rgb = np.array(Image.open(p).convert("RGB"), dtype=np.uint8)
+        if w > h:
+            x = (w - h) // 2
+            rgb = rgb[:, x:x + h]
+        elif h > w:
+            y = (h - w) // 2
+            rgb = rgb[y:y + w, :]
+        want.append(rgb if rgb.shape[:2] == (48, 48) else CR.lanczos_resize(rgb, 48, 48))
+    assert not np.array_equal(want[0], want[3])
+    still = dict(orig=tmp_path / "IMG_original.jpg",
+                 ladders={"candy": [tmp_path / f"IMG_{s}.jpg" for s, *_ in files[1:]]})
+    needs = [SM.ORIGINAL, ("candy", 0), ("candy", 1), ("candy", 2)]
+    got = SM.load_bank(still, needs, 48, False, DEV)
+    assert got.dtype == torch.uint8 and got.is_contiguous() and tuple(got.shape) == (4, 48, 48, 3)
+    assert np.array_equal(got.cpu().numpy(), np.stack(want))
+
+
+def test_wrapper_refuses_bank():
+    """The shared wrapper's messages carry this wrapper's name."""
+    good = _descriptors()[:1]
+    with pytest.raises(_lib.NstError, match=r"^style_morph_frames: expected a uint8 \[n_bank,h,w,3\] bank, got torch.float32"):
+        SM.style_morph_frames(torch.zeros((N_BANK, 4, 4, 3), dtype=torch.float32, device=DEV), good)
+    with pytest.raises(_lib.NstError, match=r"^style_morph_frames: expected a uint8 \[n_bank,h,w,3\] bank, got torch.uint8 \(4, 4, 3\)"):
+        SM.style_morph_frames(torch.zeros((4, 4, 3), dtype=torch.uint8, device=DEV), good)
+    with pytest.raises(_lib.NstError, match=r"^style_morph_frames: expected a uint8 \[n_bank,h,w,3\] bank"):
+        SM.style_morph_frames(torch.zeros((N_BANK, 4, 4, 4), dtype=torch.uint8, device=DEV), good)
