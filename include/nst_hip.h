@@ -169,6 +169,23 @@ int nst_workspace_bytes(const nst_handle* h, int n, int in_h, int in_w, size_t* 
  * call: scheduling only. */
 int nst_set_stream_split(nst_handle* h, int k);
 
+/* A test seam: launch the persistent conv kernels of nst_forward / nst_forward_capture on this handle with at most
+ * max_workgroups workgroups instead of the device-sized grid (CUs x resident workgroups), so that frames far smaller
+ * than the device walk the kernels' tile loops: each workgroup takes work items b, b + G, b + 2G, ... of its launch.
+ * The kernels are the same and an output element's arithmetic does not depend on the workgroup that computed it, so
+ * outputs are identical; only the schedule changes.  The 9x9 output conv (one work item per wave) sizes its row
+ * segments for max_workgroups x waves slots instead.  The internal streams of nst_set_stream_split see the same cap.
+ * 0 = off (the default); < 0 -> NST_E_INVALID.  Replaces no reference call. */
+int nst_set_grid_cap(nst_handle* h, int max_workgroups);
+/* The seam's arithmetic, a pure function: the grid of a launcher that would use nb workgroups, under cap (0 = off). */
+int nst_capped_blocks(int nb, int cap);
+/* What op's conv launcher did in the handle's last forward: the workgroups and work items of its last launch and how
+ * many launches it made (a batch of more frames than the kernel holds InstanceNorm tables for runs in chunks);
+ * nst_op_launch_grid gives launch 0 .. launches-1 one by one.  All 0 for an op that ran no persistent kernel (a
+ * residual add, a one-tile-per-workgroup kernel) or before any forward.  With a stream split: the last sub-batch's. */
+int nst_op_last_grid(const nst_handle* h, int op, int* blocks, int* n_work, int* launches);
+int nst_op_launch_grid(const nst_handle* h, int op, int launch, int* blocks, int* n_work);
+
 /*
  * Stylize a batch.  Replaces `model(x_in)` with its io_preset pre/post arithmetic
  * (pipeline.py:1445-1486: preset encode -> .to(device) -> model -> .cpu() -> decode -> clamp(0,1))

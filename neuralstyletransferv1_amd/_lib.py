@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "nst_camera_pulse_u8", "nst_camera_rect_subpix_u8", "nst_camera_lanczos_u8", "nst_camera_hue_u8",
     "nst_camera_smooth_u8", "nst_camera_scratch_bytes", "nst_camera_frames_u8",
     "nst_style_morph_frames", "nst_multi_model_frames",
+    "nst_set_grid_cap", "nst_capped_blocks", "nst_op_last_grid", "nst_op_launch_grid",
 )
 NST_FLOW_GAUSSIAN = 256  # cv2.OPTFLOW_FARNEBACK_GAUSSIAN (nst_flow_farneback_ex flags)
 NST_MORPH_MAX_FRAMES = 128  # frames per nst_morph_frames launch
@@ -206,6 +207,15 @@ def lib() -> ctypes.CDLL:
         L.nst_set_range_check.restype = i
         L.nst_set_stream_split.argtypes = [vp, i]
         L.nst_set_stream_split.restype = i
+        ip = ctypes.POINTER(i)
+        L.nst_set_grid_cap.argtypes = [vp, i]
+        L.nst_set_grid_cap.restype = i
+        L.nst_capped_blocks.argtypes = [i, i]
+        L.nst_capped_blocks.restype = i
+        L.nst_op_last_grid.argtypes = [vp, i, ip, ip, ip]
+        L.nst_op_last_grid.restype = i
+        L.nst_op_launch_grid.argtypes = [vp, i, i, ip, ip]
+        L.nst_op_launch_grid.restype = i
         L.nst_op_describe.argtypes = [vp, i, i, i, i, ctypes.POINTER(NstOpDesc)]
         L.nst_forward_capture.argtypes = [vp, vp, i, i, i, i, i, vp, i, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(vp),
                                           ctypes.POINTER(vp), vp]

@@ -1384,7 +1384,8 @@ struct ConvInst {
     if constexpr (PERS) {
       ConvParams p = p0;
       p.n_work = (int)(grid.x * grid.y);
-      const int nb = p.n_work < resident_blocks() ? p.n_work : resident_blocks();
+      const int nb = capped_blocks(p.n_work < resident_blocks() ? p.n_work : resident_blocks());
+      note_launch(nb, p.n_work);
       hipLaunchKernelGGL(kernel, dim3(nb), dim3(C::NT), 0, st, p);
     } else {
       hipLaunchKernelGGL(kernel, grid, dim3(C::NT), 0, st, p0);

@@ -282,7 +282,7 @@ struct Out9Inst {
     ConvParams p = p0;
     const int n = (int)grid.y;
     const int strips = (p.ow + C::SW - 1) / C::SW;
-    const int slots = cus() * NW;  // one workgroup per CU (LDS)
+    const int slots = capped_blocks(cus()) * NW;  // one workgroup per CU (LDS)
     int nseg = std::max(1, slots / std::max(1, n * strips));
     nseg = std::min(nseg, std::max(1, p.oh / 16));  // segments of >= 16 rows (8 rows of lead-in each)
     p.seg_len = (p.oh + nseg - 1) / nseg;
@@ -291,6 +291,7 @@ struct Out9Inst {
     p.tiles_y = nseg;
     p.n_work = n * nseg * strips;
     const int blocks = (p.n_work + NW - 1) / NW;
+    note_launch(blocks, p.n_work);
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * NW), 0, st, p);
   }
   static ConvKernelInfo info() {

@@ -545,7 +545,8 @@ struct WphaseInst {
       if (p0.res_rnorm) p.res_rnorm = p0.res_rnorm + (size_t)f0 * p0.cs;
       p.partial = p0.partial + (size_t)f0 * ntile * 4 * p0.cout_stride * 2;
       p.n_work = nf * ntile;
-      const int nb = std::min(p.n_work, cus());
+      const int nb = capped_blocks(std::min(p.n_work, cus()));
+      note_launch(nb, p.n_work);
       const bool zp = p.axis_mode == AX_ZERO;  // ConvTranspose: zeros past the edge
       if constexpr (RES) {
         // the join of a normalised stream (WF_RESRN) is not instantiated: it spilled (12-16 B of scratch per lane

@@ -288,7 +288,8 @@ struct Ws1sInst {
   static void launch(const ConvParams& p0, dim3 grid, hipStream_t st) {
     ConvParams p = p0;
     p.n_work = (int)grid.x * (int)grid.y;
-    const int nb = std::min(p.n_work, cus());  // one workgroup per CU
+    const int nb = capped_blocks(std::min(p.n_work, cus()));  // one workgroup per CU
+    note_launch(nb, p.n_work);
     const bool zp = p.axis_mode == AX_ZERO || p.axis_mode == AX_ZERO_PREREFLECT;
     if (p.in_norm != nullptr)
       zp ? go<true, true>(p, nb, st) : go<false, true>(p, nb, st);

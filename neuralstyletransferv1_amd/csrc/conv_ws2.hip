@@ -438,7 +438,8 @@ struct Ws2Inst {
   static void launch(const ConvParams& p0, dim3 grid, hipStream_t st) {
     ConvParams p = p0;
     p.n_work = (int)grid.x * (int)grid.y;
-    const int nb = std::min(p.n_work, cus() * (OCC * 4 / C::NW));  // workgroups resident per CU
+    const int nb = capped_blocks(std::min(p.n_work, cus() * (OCC * 4 / C::NW)));  // workgroups resident per CU
+    note_launch(nb, p.n_work);
     // the narrow-input form serves ReCoNet's reflection-padded layer only (its zero-padded instantiation spills at
     // three waves per SIMD): nst_api selects it for that net alone
     if constexpr (CLD == CINP) {

@@ -436,7 +436,8 @@ struct Ws9Inst {
   static void launch(const ConvParams& p0, dim3 grid, hipStream_t st) {
     ConvParams p = p0;
     p.n_work = (int)grid.x * (int)grid.y;
-    const int nb = std::min(p.n_work, cus() * (8 / NW));  // 8 waves per CU (VGPRs)
+    const int nb = capped_blocks(std::min(p.n_work, cus() * (8 / NW)));  // 8 waves per CU (VGPRs)
+    note_launch(nb, p.n_work);
     hipLaunchKernelGGL((ws9_kernel<T, NW, SW, O32, CO, CST>), dim3(nb), dim3(C::NT), 0, st, p);
   }
   static ConvKernelInfo info() {

@@ -573,7 +573,8 @@ struct Wst16Inst {
       if (p0.in_norm) p.in_norm = p0.in_norm + (size_t)f0 * p0.cs;
       p.partial = p0.partial + (size_t)f0 * ntile * p0.cout_stride * 2;
       p.n_work = nf * ntile;
-      const int nb = std::min(p.n_work, cus());
+      const int nb = capped_blocks(std::min(p.n_work, cus()));
+      note_launch(nb, p.n_work);
       const bool zp = p.axis_mode != AX_REFLECT;
 #if NST_W32_MIN
       // experiment build: the Johnson trunk's three variants only (reflection padding)

@@ -24,6 +24,31 @@ namespace nst {
 static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
 
+// nst_set_grid_cap: the calling thread's cap and the op record its launchers report to (GridScope below sets both)
+static thread_local int g_grid_cap = 0;
+static thread_local std::vector<std::pair<int, int>>* g_grid_log = nullptr;
+int capped_blocks(int nb) { return nst_capped_blocks(nb, g_grid_cap); }
+void note_launch(int blocks, int n_work) {
+  if (g_grid_log) g_grid_log->emplace_back(blocks, n_work);
+}
+namespace {
+// one conv launch of a forward: the handle's cap and the op's record, restored on the way out
+struct GridScope {
+  int cap0;
+  std::vector<std::pair<int, int>>* log0;
+  GridScope(int cap, std::vector<std::pair<int, int>>* log) : cap0(g_grid_cap), log0(g_grid_log) {
+    g_grid_cap = cap;
+    g_grid_log = log;
+  }
+  ~GridScope() {
+    g_grid_cap = cap0;
+    g_grid_log = log0;
+  }
+  GridScope(const GridScope&) = delete;
+  GridScope& operator=(const GridScope&) = delete;
+};
+}  // namespace
+
 const ConvKernelInfo* conv_table_bf16(int* count);
 const ConvKernelInfo* conv_table_f16(int* count);
 const ConvKernelInfo* conv_table_bf16_wl(int* count);
@@ -299,6 +324,9 @@ struct nst_handle {
   float t7_mul = 0.f;  // nn.MulConstant's constant_scalar (NST_ARCH_TORCH7_*)
   hipStream_t sub[NST_MAX_STREAM_SPLIT] = {};
   hipEvent_t fork = nullptr, join[NST_MAX_STREAM_SPLIT] = {};
+  // nst_set_grid_cap (a test seam) and what each op's launcher did in the last forward: {blocks, n_work} per launch
+  int grid_cap = 0;
+  std::vector<std::vector<std::pair<int, int>>> grids;
 };
 
 struct nst_lab {
@@ -1312,6 +1340,39 @@ int nst_set_stream_split(nst_handle* h, int k) {
   return NST_OK;
 }
 
+int nst_capped_blocks(int nb, int cap) { return cap > 0 && cap < nb ? cap : nb; }
+
+int nst_set_grid_cap(nst_handle* h, int max_workgroups) {
+  if (!h || max_workgroups < 0) { set_error("nst_set_grid_cap: invalid arguments"); return NST_E_INVALID; }
+  h->grid_cap = max_workgroups;
+  return NST_OK;
+}
+
+int nst_op_last_grid(const nst_handle* h, int op, int* blocks, int* n_work, int* launches) {
+  if (!h || !blocks || !n_work || !launches || op < 0 || op >= (int)h->prog.size()) {
+    set_error("nst_op_last_grid: invalid arguments");
+    return NST_E_INVALID;
+  }
+  *blocks = *n_work = *launches = 0;
+  if ((size_t)op < h->grids.size() && !h->grids[op].empty()) {
+    *blocks = h->grids[op].back().first;
+    *n_work = h->grids[op].back().second;
+    *launches = (int)h->grids[op].size();
+  }
+  return NST_OK;
+}
+
+int nst_op_launch_grid(const nst_handle* h, int op, int launch, int* blocks, int* n_work) {
+  if (!h || !blocks || !n_work || op < 0 || (size_t)op >= h->grids.size() || launch < 0 ||
+      (size_t)launch >= h->grids[op].size()) {
+    set_error("nst_op_launch_grid: invalid arguments");
+    return NST_E_INVALID;
+  }
+  *blocks = h->grids[op][launch].first;
+  *n_work = h->grids[op][launch].second;
+  return NST_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -1514,7 +1575,10 @@ int forward_impl(nst_handle* h, const void* x, int x_fmt, int n, int in_h, int i
       NST_HIP_CHECK(hipEventCreate(&rec.b));
       NST_HIP_CHECK(hipEventRecord(rec.a, st));
     }
-    k->launch(p, grid, st);
+    {
+      GridScope gs(h->grid_cap, &h->grids[i]);
+      k->launch(p, grid, st);
+    }
     hipError_t e = hipGetLastError();
     if (h->profiling && e == hipSuccess) {
       NST_HIP_CHECK(hipEventRecord(rec.b, st));
@@ -1549,6 +1613,9 @@ int forward_impl(nst_handle* h, const void* x, int x_fmt, int n, int in_h, int i
     return NST_OK;
   };
   if (h->range_flag) NST_HIP_CHECK(hipMemsetAsync(h->range_flag, 0, sizeof(int), st));
+  // this forward's launch record (a stream split keeps its last sub-batch's); cleared in place: no allocation per call
+  h->grids.resize(h->prog.size());
+  for (auto& g : h->grids) g.clear();
   for (size_t i = 0; i < h->prog.size(); ++i) {
     const int rc = run_op(i);
     if (rc != NST_OK) return rc;

@@ -152,6 +152,14 @@ struct ConvKernelInfo {
   void (*launch)(const ConvParams&, dim3 grid, hipStream_t);
 };
 
+// ---- nst_set_grid_cap (a test seam; host state only, defined in nst_api.cpp) ----
+// The forward entry points set the calling thread's cap from the handle around each conv launch (every stream of
+// nst_set_stream_split is launched from that thread, so all see it) and restore it afterwards; outside them it is 0.
+// capped_blocks: the grid a persistent launcher uses for nb resident workgroups, min(nb, cap) with the cap on.
+// note_launch: a persistent launcher (and conv_out9's) reports each launch's grid to the op record being run.
+int capped_blocks(int nb);
+void note_launch(int blocks, int n_work);
+
 // Look up a compiled instantiation; nullptr if the combination was not built.
 const ConvKernelInfo* find_conv_kernel(int dtype, int mode, int ks, int stride, int cinp, int bn, int in_kind,
                                        int out_kind, int res = 0, bool no_persistent = false);

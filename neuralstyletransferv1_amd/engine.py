@@ -99,6 +99,29 @@ class Engine:
         """nst_set_stream_split: run each batch as k sub-batches on the library's internal streams (1 = whole)."""
         check(lib().nst_set_stream_split(self._h, int(k)), "nst_set_stream_split")
 
+    def set_grid_cap(self, k: int) -> None:
+        """nst_set_grid_cap (a test seam): at most k workgroups per persistent conv launch, so that small frames
+        walk the kernels' tile loops; 0 = off (the device-sized grid)."""
+        check(lib().nst_set_grid_cap(self._h, int(k)), "nst_set_grid_cap")
+
+    def op_grids(self):
+        """What each op's conv launcher last did (nst_op_last_grid / nst_op_launch_grid): per op {"blocks",
+        "n_work": of its last launch, "launches", "per_launch": [(blocks, n_work)] of a batch launched in frame
+        chunks}; all zero for an op that ran no persistent kernel."""
+        out = []
+        for i in range(lib().nst_num_ops(self._h)):
+            b, w, k = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+            check(lib().nst_op_last_grid(self._h, i, ctypes.byref(b), ctypes.byref(w), ctypes.byref(k)),
+                  "nst_op_last_grid")
+            per = []
+            for j in range(k.value):
+                bj, wj = ctypes.c_int(), ctypes.c_int()
+                check(lib().nst_op_launch_grid(self._h, i, j, ctypes.byref(bj), ctypes.byref(wj)),
+                      "nst_op_launch_grid")
+                per.append((bj.value, wj.value))
+            out.append({"blocks": b.value, "n_work": w.value, "launches": k.value, "per_launch": per})
+        return out
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value:
@@ -151,7 +174,8 @@ class Engine:
     def forward_capture(self, x: torch.Tensor, x_fmt: str, preset: str, y_fmt: str):
         """nst_forward_capture: run the batch and return (y, ops, captures); captures[i] =
         {"act": raw conv output of op i [n,oh,ow,cout_stride] (bf16/fp32), "res": joined residual
-        stream it wrote or None, "stats": [n,cout_stride,2] fp32 {scale, shift} or None}."""
+        stream it wrote or None, "stats": [n,cout_stride,2] fp32 {scale, shift} or None}; ops[i]["grid"] = what op
+        i's launcher did in this run (op_grids)."""
         _lib.require_gpu_tensor(x, "input")
         x = x.contiguous()
         if x_fmt == "u8":
@@ -193,6 +217,8 @@ class Engine:
         check(lib().nst_forward_capture(self._h, x.data_ptr(), xf, n, h, w, _lib.PRESETS[preset], y.data_ptr(), yf,
                                         ws.data_ptr(), ws.numel(), act, res, st, _lib.stream_ptr(self.device)),
               "nst_forward_capture")
+        for d, g in zip(ops, self.op_grids()):  # next to each op's record: the grid its launcher used
+            d["grid"] = g
         return y, ops, caps
 
     def forward_tensor(self, x: torch.Tensor) -> torch.Tensor:

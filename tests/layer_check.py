@@ -206,6 +206,8 @@ def check_layers(net, frames_u8: np.ndarray, preset: str, bands: Optional[Sequen
         row_sets = [(0, ch)] if bands is None else sorted({
             (r0, min(ch, r0 + k)) for f, k in bands for r0 in [min(max(0, int(f * ch)) // 2 * 2, max(0, ch - k) // 2 * 2)]})
         rec = {"op": i, "layer": conv, "mode": d["kernel_mode"], "elements": 0}
+        g = d["grid"]  # the grid the op's launcher used in the captured run (tests/test_gpu_walk.py)
+        rec.update(blocks=g["blocks"], n_work=g["n_work"], launches=g["launches"])
         if frn:  # TLU outputs are stored shifted by -tau: the bias absorbs sum W tau
             bias = _frn_bias(sd, d["layer"], W, bias)
         for (r0, r1) in row_sets:

@@ -8,6 +8,12 @@ truncation), and on ReCoNet (InstanceNorm and FRN/TLU) the generic bf16 kernels.
 outputs within 1 bf16 ulp (or 4e-6 of the layer's max |value| where the sum cancels), <= 0.1 % of
 elements 1 ulp off (measured <= 0.03 %), IN statistics within 1e-5, joined residual streams bit-exact, raw fp32 output
 within 5e-6, u8 frames >= 99.99 % identical and never more than 1 LSB off.
+
+The persistent kernels size their grid by the device (256 CUs, x2 for ws9 and ws2), and the small shapes here have far
+fewer work items (johnson 2x70x90: 36 for ws9, 30 for ws2, 6 for wst16), so in this file only the 1080p and 4K tests
+give a workgroup a second work item.  tests/test_gpu_walk.py runs the same check with the grid capped
+(nst_set_grid_cap, a test seam), so the kernels' tile walks are held to the same bars at small shapes: several frames,
+ragged last tile columns and rows, in seconds.
 """
 import numpy as np
 import pytest

@@ -362,3 +362,21 @@ def test_fast_png_writer_decodes_to_the_same_pixels(shape, tmp_path):
         assert got.dtype == np.uint8 and np.array_equal(got, a), kind
     with pytest.raises(ValueError):
         pngio.encode_png(np.zeros((4, 4, 3), np.float32))
+
+
+def test_capped_blocks():
+    """nst_set_grid_cap's arithmetic (nst_capped_blocks, the function every persistent launcher's grid goes
+    through): off, above the launcher's own grid, below it, and one workgroup; and the null-handle refusals."""
+    from neuralstyletransferv1_amd import _lib
+    L = _lib.lib()
+    for nb in (1, 2, 6, 36, 256, 512):
+        assert L.nst_capped_blocks(nb, 0) == nb            # off: the launcher's own grid
+        assert L.nst_capped_blocks(nb, nb + 1) == nb       # a cap above it changes nothing
+        assert L.nst_capped_blocks(nb, nb) == nb
+        assert L.nst_capped_blocks(nb, 1) == 1             # one workgroup walks every work item
+        for cap in (2, 5, 8, 16):
+            assert L.nst_capped_blocks(nb, cap) == min(nb, cap)
+    assert L.nst_set_grid_cap(None, 0) == _lib.NST_E_INVALID
+    assert b"nst_set_grid_cap" in L.nst_last_error()
+    assert L.nst_op_last_grid(None, 0, None, None, None) == _lib.NST_E_INVALID
+    assert L.nst_op_launch_grid(None, 0, 0, None, None) == _lib.NST_E_INVALID
