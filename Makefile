@@ -18,7 +18,7 @@ LIB := $(PKG)/libnst_hip.so
 
 all: $(LIB)
 
-$(BUILD)/%.hip.o: $(CSRC)/%.hip $(CSRC)/conv_impl.h $(CSRC)/conv_ws_common.h $(CSRC)/conv_tab16.h $(CSRC)/conv_tab32.h $(CSRC)/nst_internal.h $(CSRC)/seg_internal.h $(CSRC)/post_common.h $(CSRC)/region_internal.h $(CSRC)/flow_internal.h $(CSRC)/blur_internal.h include/nst_hip.h
+$(BUILD)/%.hip.o: $(CSRC)/%.hip $(CSRC)/conv_impl.h $(CSRC)/conv_launch.h $(CSRC)/conv_ws_common.h $(CSRC)/conv_tab16.h $(CSRC)/conv_tab32.h $(CSRC)/nst_internal.h $(CSRC)/seg_internal.h $(CSRC)/post_common.h $(CSRC)/region_internal.h $(CSRC)/flow_internal.h $(CSRC)/blur_internal.h include/nst_hip.h
 	@mkdir -p $(BUILD)
 	$(if $(NOSCRATCH),$(HIPCC) $(CXXFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $@.rem && python3 tools/check_scratch.py $@.rem || { rm -f $@; exit 1; },$(HIPCC) $(CXXFLAGS) -c $< -o $@)
 
@@ -29,11 +29,11 @@ $(BUILD)/conv_wphase.hip.o $(BUILD)/conv_ws9.hip.o $(BUILD)/conv_gemm.hip.o $(BU
 # the persistent kernels fully unroll a long K loop (static register / LDS indices): lift the
 # pragma-unroll size cap for that translation unit only
 $(BUILD)/conv_bf16_wl.hip.o: CXXFLAGS += -mllvm -pragma-unroll-threshold=200000
-$(BUILD)/conv_wst16_p%.hip.o: $(CSRC)/conv_wst16.hip $(CSRC)/conv_impl.h $(CSRC)/conv_ws_common.h include/nst_hip.h
+$(BUILD)/conv_wst16_p%.hip.o: $(CSRC)/conv_wst16.hip $(CSRC)/conv_impl.h $(CSRC)/conv_launch.h $(CSRC)/conv_ws_common.h include/nst_hip.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(CXXFLAGS) -mllvm -pragma-unroll-threshold=5000000 -DNST_W16_PART=$* -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $@.rem && python3 tools/check_scratch.py $@.rem || { rm -f $@; exit 1; }
 # part 8: launchers and table only (every kernel an extern template: no kernel, no resource remarks)
-$(BUILD)/conv_wst16_p8.hip.o: $(CSRC)/conv_wst16.hip $(CSRC)/conv_impl.h $(CSRC)/conv_ws_common.h include/nst_hip.h
+$(BUILD)/conv_wst16_p8.hip.o: $(CSRC)/conv_wst16.hip $(CSRC)/conv_impl.h $(CSRC)/conv_launch.h $(CSRC)/conv_ws_common.h include/nst_hip.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(CXXFLAGS) -DNST_W16_PART=8 -c $< -o $@
 $(BUILD)/conv_wphase.hip.o: CXXFLAGS += -mllvm -pragma-unroll-threshold=5000000
@@ -88,7 +88,7 @@ clean:
 STAMP_TAG ?= stamp
 STAMP_FLAGS ?=
 STAMP_LIB := $(PKG)/libnst_hip_$(STAMP_TAG).so
-build/$(STAMP_TAG)/conv_wst16.hip.o: $(CSRC)/conv_wst16.hip $(CSRC)/conv_impl.h $(CSRC)/conv_ws_common.h include/nst_hip.h
+build/$(STAMP_TAG)/conv_wst16.hip.o: $(CSRC)/conv_wst16.hip $(CSRC)/conv_impl.h $(CSRC)/conv_launch.h $(CSRC)/conv_ws_common.h include/nst_hip.h
 	@mkdir -p build/$(STAMP_TAG)
 	$(HIPCC) $(CXXFLAGS) -mllvm -pragma-unroll-threshold=5000000 -DNST_WST32_STAMP=1 $(STAMP_FLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $@.rem && python3 tools/check_scratch.py $@.rem
 $(STAMP_LIB): build/$(STAMP_TAG)/conv_wst16.hip.o $(filter-out $(W16_OBJS),$(OBJS))

@@ -39,6 +39,7 @@
 #include <type_traits>
 #include "nst_internal.h"
 #include "nst_hip.h"
+#include "conv_launch.h"
 
 // generic non-persistent fills with per-item channel chunks read the producer's IN constants from an LDS table
 #ifndef NST_GEN_NTAB
@@ -1372,11 +1373,9 @@ struct ConvInst {
   // resident workgroups of the persistent form on this device (CUs x occupancy)
   static int resident_blocks() {
     static const int slots = [] {
-      int dev = 0, cus = 0, occ = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
+      int occ = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, C::NT, 0) != hipSuccess || occ < 1) occ = 1;
-      return cus * occ;
+      return device_cus() * occ;
     }();
     return slots;
   }
@@ -1384,27 +1383,22 @@ struct ConvInst {
     if constexpr (PERS) {
       ConvParams p = p0;
       p.n_work = (int)(grid.x * grid.y);
-      const int nb = capped_blocks(p.n_work < resident_blocks() ? p.n_work : resident_blocks());
-      note_launch(nb, p.n_work);
+      const int nb = persistent_grid(p.n_work, resident_blocks());
       hipLaunchKernelGGL(kernel, dim3(nb), dim3(C::NT), 0, st, p);
     } else {
       hipLaunchKernelGGL(kernel, grid, dim3(C::NT), 0, st, p0);
     }
   }
   static ConvKernelInfo info() {
-    ConvKernelInfo k;
-    std::memset(&k, 0, sizeof(k));  // fields this mapping does not set (wbytes, tanh_out, in/out_esz, ...) are 0
-    k.dtype = dtype_code<T>();
-    k.mode = MODE;
+    // fields this mapping does not set (wbytes, tanh_out, in/out_esz, ...) are 0
+    ConvKernelInfo k = conv_info(dtype_code<T>(), MODE, &launch, PERS);
     k.ks = KS; k.stride = S; k.cinp = CINP; k.bn = BN; k.th = TH; k.tw = TW; k.wm = WM; k.wn = WN;
     k.in_kind = INK; k.out_kind = OUTK;
     k.pair = C::PAIR ? 1 : 0; k.nch = C::NCH; k.cpc = C::CPC; k.kp = C::KP; k.nchunk = C::NCHUNK;
     k.nstep = C::NSTEP; k.nstep_pack = C::NSTEP_PACK; k.nsubt = C::NSUBT; k.nsub = C::NSUB; k.lds_bytes = C::LDS_ALLOC;
-    k.persistent = PERS ? 1 : 0;
     k.korder = PERS ? 1 : 0;
     k.part_rows = PERS ? C::REDW : 1;
     k.res = (VAR & VAR_RES) != 0 ? 1 : 0;
-    k.launch = &launch;
     return k;
   }
 };

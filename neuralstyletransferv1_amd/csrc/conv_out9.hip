@@ -20,7 +20,6 @@
 // normalised (producer InstanceNorm + ReLU) and written to the other ring slot at its end.  The
 // 9x9 weights (one copy, 15.5 KB bf16 for C = 32) sit in LDS for the whole kernel.
 #include <algorithm>
-#include <cstring>
 
 #include "conv_impl.h"
 
@@ -268,21 +267,12 @@ template <typename T, int CINP, int G, int NW, int OUTK, bool TANH, int CLD = CI
 struct Out9Inst {
   using C = Out9Cfg<CINP, G, NW, IS_SPLIT<T> ? 4 : 2>;
   static constexpr auto kernel = out9_kernel<T, CINP, G, NW, OUTK, TANH, CLD>;
-  static int cus() {
-    static const int v = [] {
-      int dev = 0, c = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        c = 256;
-      return c;
-    }();
-    return v;
-  }
   // grid.y = frames (one channel block); the segment count fills the chip's wave slots once
   static void launch(const ConvParams& p0, dim3 grid, hipStream_t st) {
     ConvParams p = p0;
     const int n = (int)grid.y;
     const int strips = (p.ow + C::SW - 1) / C::SW;
-    const int slots = capped_blocks(cus()) * NW;  // one workgroup per CU (LDS)
+    const int slots = capped_blocks(device_cus()) * NW;  // one workgroup per CU (LDS)
     int nseg = std::max(1, slots / std::max(1, n * strips));
     nseg = std::min(nseg, std::max(1, p.oh / 16));  // segments of >= 16 rows (8 rows of lead-in each)
     p.seg_len = (p.oh + nseg - 1) / nseg;
@@ -295,19 +285,14 @@ struct Out9Inst {
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * NW), 0, st, p);
   }
   static ConvKernelInfo info() {
-    ConvKernelInfo k;
-    std::memset(&k, 0, sizeof(k));
-    k.dtype = dtype_code<T>();
-    k.mode = MODE_KYROT;
+    ConvKernelInfo k = conv_info(dtype_code<T>(), MODE_KYROT, &launch, /*persistent=*/false);  // no walk
     k.ks = 9; k.stride = 1; k.cinp = CLD; k.bn = 16;
     k.cinp_k = CLD != CINP ? CINP : 0; k.th = 1; k.tw = C::SW; k.wm = NW; k.wn = 1;
-    k.in_kind = IN_ACT; k.out_kind = OUTK;
+    k.out_kind = OUTK;
     k.cpc = C::CPCH; k.nch = C::NCH; k.lds_bytes = C::LDS;
     k.in_esz = IS_SPLIT<T> ? 4 : 0;
     k.wbytes = C::W_BYTES;
-    k.part_rows = 1;
     k.tanh_out = TANH ? 1 : 0;
-    k.launch = &launch;
     return k;
   }
 };

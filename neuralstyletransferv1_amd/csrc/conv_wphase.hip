@@ -20,7 +20,6 @@
 //     schedule serves 2, 3 or 4 parts (three parts: six slots, one per unit).
 //   * one InstanceNorm partial row per phase and tile (part_rows = 4).
 #include <algorithm>
-#include <cstring>
 
 #include "conv_ws_common.h"
 
@@ -514,39 +513,17 @@ __global__ __launch_bounds__(512) void wphase_kernel(ConvParams p) {
 template <typename T, int CINP, int COUT, int TH, int NF, bool RES, int CST = COUT>
 struct WphaseInst {
   using C = WpCfg<CINP, COUT, TH, NF, RES ? 2 : 1>;
-  static int cus() {
-    static const int v = [] {
-      int dev = 0, c = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        c = 256;
-      return c;
-    }();
-    return v;
-  }
   template <int FILL, bool ZPAD>
   static void go(const ConvParams& p, int nb, hipStream_t st) {
     hipLaunchKernelGGL((wphase_kernel<T, CINP, COUT, TH, NF, FILL, ZPAD, CST>), dim3(nb), dim3(C::NT), 0, st, p);
   }
-  // grid.x = source tiles per frame, grid.y = frames; chunks of <= NFMAX frames per launch
+  // grid.x = source tiles per frame, grid.y = frames; chunks of <= NFMAX frames per launch (the LDS IN tables'
+  // capacity) and a launch's input below 2^31 bytes (32-bit request offsets; 0x80000000 is the out-of-range
+  // offset); one workgroup per CU, four partial rows per tile
   static void launch(const ConvParams& p0, dim3 grid, hipStream_t st) {
-    const int ntile = (int)grid.x, n = (int)grid.y;
-    const size_t fin = (size_t)p0.hs * p0.ws * p0.cs * 2, fout = (size_t)p0.oh * p0.ow * p0.cout_stride * 2;
-    // frames per launch: the LDS IN tables' capacity, and a launch's input below 2^31 bytes (32-bit
-    // request offsets; 0x80000000 is the out-of-range offset)
-    const int fmax = (int)std::min<size_t>(C::NFMAX, (size_t)0x7FFFFF00u / std::max<size_t>(fin, 1));
-    if (fmax < 1) return;  // nst_api validates sizes before launching
-    for (int f0 = 0; f0 < n; f0 += fmax) {
-      const int nf = std::min(fmax, n - f0);
-      ConvParams p = p0;
-      p.in = (const char*)p0.in + f0 * fin;
-      p.out = (char*)p0.out + f0 * fout;
-      if (p0.res_r) p.res_r = (const char*)p0.res_r + f0 * fin;
-      if (p0.in_norm) p.in_norm = p0.in_norm + (size_t)f0 * p0.cs;
-      if (p0.res_rnorm) p.res_rnorm = p0.res_rnorm + (size_t)f0 * p0.cs;
-      p.partial = p0.partial + (size_t)f0 * ntile * 4 * p0.cout_stride * 2;
-      p.n_work = nf * ntile;
-      const int nb = capped_blocks(std::min(p.n_work, cus()));
-      note_launch(nb, p.n_work);
+    const size_t fin = (size_t)p0.hs * p0.ws * p0.cs * 2;
+    launch_frame_chunks(p0, (int)grid.x, (int)grid.y, C::NFMAX, (size_t)0x7FFFFF00u / std::max<size_t>(fin, 1), 4,
+                        device_cus(), [st](const ConvParams& p, int nb) {
       const bool zp = p.axis_mode == AX_ZERO;  // ConvTranspose: zeros past the edge
       if constexpr (RES) {
         // the join of a normalised stream (WF_RESRN) is not instantiated: it spilled (12-16 B of scratch per lane
@@ -559,22 +536,16 @@ struct WphaseInst {
         else
           zp ? go<WF_RAW, true>(p, nb, st) : go<WF_RAW, false>(p, nb, st);
       }
-    }
+    });
   }
   static ConvKernelInfo info() {
-    ConvKernelInfo k;
-    std::memset(&k, 0, sizeof(k));
-    k.dtype = dtype_code<T>();
-    k.mode = MODE_WPHASE;
+    ConvKernelInfo k = conv_info(dtype_code<T>(), MODE_WPHASE, &launch);
     k.ks = 3; k.stride = 1; k.cinp = CINP; k.bn = CST; k.th = TH; k.tw = C::TW; k.wm = 1; k.wn = C::NW;
     k.bn_k = CST != COUT ? COUT : 0;
-    k.in_kind = IN_ACT; k.out_kind = OUT_ACT;
     k.cpc = 8; k.nch = C::NCH; k.lds_bytes = C::LDS;
     k.wbytes = C::WBYTES;
-    k.persistent = 1;
     k.part_rows = 4;
     k.res = RES ? 1 : 0;
-    k.launch = &launch;
     return k;
   }
 };

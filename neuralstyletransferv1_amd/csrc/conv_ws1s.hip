@@ -17,8 +17,6 @@
 //   * the next tile's halo is loaded into registers (16 B = 4 fp32 channels per slot) before the MFMAs and
 //     written (normalised, split) after them, as conv_ws2.hip's fill; output tile staged in LDS (16-B chunks
 //     XOR-swizzled by pixel) and stored as whole 512-B pixels.
-#include <algorithm>
-#include <cstring>
 
 #include "conv_ws_common.h"
 
@@ -271,15 +269,6 @@ __global__ __launch_bounds__(512, 1) void ws1s_kernel(ConvParams p) {
 template <int TH>
 struct Ws1sInst {
   using C = W1sCfg<TH>;
-  static int cus() {
-    static const int v = [] {
-      int dev = 0, c = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        c = 256;
-      return c;
-    }();
-    return v;
-  }
   template <bool ZPAD, bool NRM>
   static void go(const ConvParams& p, int nb, hipStream_t st) {
     hipLaunchKernelGGL((ws1s_kernel<TH, ZPAD, NRM>), dim3(nb), dim3(C::NT), 0, st, p);
@@ -288,8 +277,7 @@ struct Ws1sInst {
   static void launch(const ConvParams& p0, dim3 grid, hipStream_t st) {
     ConvParams p = p0;
     p.n_work = (int)grid.x * (int)grid.y;
-    const int nb = capped_blocks(std::min(p.n_work, cus()));  // one workgroup per CU
-    note_launch(nb, p.n_work);
+    const int nb = persistent_grid(p.n_work, device_cus());  // one workgroup per CU
     const bool zp = p.axis_mode == AX_ZERO || p.axis_mode == AX_ZERO_PREREFLECT;
     if (p.in_norm != nullptr)
       zp ? go<true, true>(p, nb, st) : go<false, true>(p, nb, st);
@@ -297,19 +285,12 @@ struct Ws1sInst {
       zp ? go<true, false>(p, nb, st) : go<false, false>(p, nb, st);
   }
   static ConvKernelInfo info() {
-    ConvKernelInfo k;
-    std::memset(&k, 0, sizeof(k));
-    k.dtype = NST_KDT_SPLITO_O32;
-    k.mode = MODE_WS1S;
+    ConvKernelInfo k = conv_info(NST_KDT_SPLITO_O32, MODE_WS1S, &launch);
     k.ks = 3; k.stride = 1; k.cinp = C::CINP; k.bn = C::COUT; k.th = TH; k.tw = C::TW; k.wm = 1; k.wn = C::NW;
-    k.in_kind = IN_ACT; k.out_kind = OUT_ACT;
     k.cpc = 8; k.nch = C::NCH; k.lds_bytes = C::LDS;
     k.wbytes = C::WBYTES;
-    k.persistent = 1;
-    k.part_rows = 1;
     k.in_esz = 4;
     k.out_esz = 4;
-    k.launch = &launch;
     return k;
   }
 };

@@ -25,8 +25,6 @@
 //   * output tile staged in LDS (8-byte slots XOR-swizzled by pixel: epilogue writes 2-way, store
 //     reads conflict-free; a 32-byte wave-slot swizzle was 4-way on the writes) and stored as whole pixels,
 //     16 B per lane; one InstanceNorm partial row per tile and row group.
-#include <algorithm>
-#include <cstring>
 
 #include "conv_ws_common.h"
 
@@ -425,21 +423,11 @@ template <typename T, int CINP, int COUT, int TH, int OCC, bool SPL = false, boo
           int CLD = CINP>
 struct Ws2Inst {
   using C = W2Cfg<CINP, COUT, TH, SPL, O32>;
-  static int cus() {
-    static const int v = [] {
-      int dev = 0, c = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        c = 256;
-      return c;
-    }();
-    return v;
-  }
   // grid.x = output tiles per frame, grid.y = frames
   static void launch(const ConvParams& p0, dim3 grid, hipStream_t st) {
     ConvParams p = p0;
     p.n_work = (int)grid.x * (int)grid.y;
-    const int nb = capped_blocks(std::min(p.n_work, cus() * (OCC * 4 / C::NW)));  // workgroups resident per CU
-    note_launch(nb, p.n_work);
+    const int nb = persistent_grid(p.n_work, device_cus() * (OCC * 4 / C::NW));  // workgroups resident per CU
     // the narrow-input form serves ReCoNet's reflection-padded layer only (its zero-padded instantiation spills at
     // three waves per SIMD): nst_api selects it for that net alone
     if constexpr (CLD == CINP) {
@@ -451,21 +439,15 @@ struct Ws2Inst {
     hipLaunchKernelGGL((ws2_kernel<T, CINP, COUT, TH, false, OCC, SPL, O32, PF, CLD>), dim3(nb), dim3(C::NT), 0, st, p);
   }
   static ConvKernelInfo info() {
-    ConvKernelInfo k;
-    std::memset(&k, 0, sizeof(k));
-    k.dtype = SPL ? (O32 ? NST_KDT_SPLIT_O32 : NST_KDT_SPLIT_O16) : dtype_code<T>();
+    ConvKernelInfo k = conv_info(SPL ? (O32 ? NST_KDT_SPLIT_O32 : NST_KDT_SPLIT_O16) : dtype_code<T>(), MODE_WS2, &launch);
     k.in_esz = C::IESZ;
     k.out_esz = O32 ? 4 : 2;
     k.split_w = SPL ? 1 : 0;
-    k.mode = MODE_WS2;
     k.ks = 3; k.stride = 2; k.cinp = CLD; k.bn = COUT;
     k.cinp_k = CLD != CINP ? CINP : 0; k.th = TH; k.tw = C::TW; k.wm = C::NRG; k.wn = C::NCG;
-    k.in_kind = IN_ACT; k.out_kind = OUT_ACT;
     k.cpc = SPL ? 4 : 8; k.nch = C::NCH; k.lds_bytes = C::LDS;
     k.wbytes = C::WBYTES;
-    k.persistent = 1;
     k.part_rows = C::NRG;
-    k.launch = &launch;
     return k;
   }
 };

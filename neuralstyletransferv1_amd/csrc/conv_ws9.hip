@@ -28,8 +28,6 @@
 //     pixels, 16 B per lane (half-pixel stores from the accumulators measured ~3 % slower);
 //     per-wave IN partials (DPP reduce-scatter) combined in fixed order into one partial row per
 //     tile.  Measured (bench, 8 x 1080p): 0.367 ms vs 0.51 for the generic kernel.
-#include <algorithm>
-#include <cstring>
 #include <type_traits>
 
 #include "conv_ws_common.h"
@@ -423,40 +421,23 @@ __global__ __launch_bounds__(64 * NW, WS9_OCC) void ws9_kernel(ConvParams p) {
 template <typename T, int NW, bool SW = false, bool O32 = false, int CO = 32, int CST = CO>
 struct Ws9Inst {
   using C = W9Cfg<NW, SW, O32, CO>;
-  static int cus() {
-    static const int v = [] {
-      int dev = 0, c = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        c = 256;
-      return c;
-    }();
-    return v;
-  }
   // grid.x = output tiles per frame, grid.y = frames
   static void launch(const ConvParams& p0, dim3 grid, hipStream_t st) {
     ConvParams p = p0;
     p.n_work = (int)grid.x * (int)grid.y;
-    const int nb = capped_blocks(std::min(p.n_work, cus() * (8 / NW)));  // 8 waves per CU (VGPRs)
-    note_launch(nb, p.n_work);
+    const int nb = persistent_grid(p.n_work, device_cus() * (8 / NW));  // 8 waves per CU (VGPRs)
     hipLaunchKernelGGL((ws9_kernel<T, NW, SW, O32, CO, CST>), dim3(nb), dim3(C::NT), 0, st, p);
   }
   static ConvKernelInfo info() {
-    ConvKernelInfo k;
-    std::memset(&k, 0, sizeof(k));
-    k.dtype = SW ? (O32 ? NST_KDT_SW_O32 : NST_KDT_SW_O16) : dtype_code<T>();
-    k.mode = MODE_WS9;
+    ConvKernelInfo k = conv_info(SW ? (O32 ? NST_KDT_SW_O32 : NST_KDT_SW_O16) : dtype_code<T>(), MODE_WS9, &launch);
     k.ks = 9; k.stride = 1; k.cinp = 4; k.bn = CST; k.th = C::TH; k.tw = C::TW; k.wm = 1; k.wn = C::NW;
     k.bn_k = CST != CO ? CO : 0;
     k.in_esz = 2;
     k.out_esz = O32 ? 4 : 2;
     k.split_w = SW ? 1 : 0;
-    k.in_kind = IN_ACT; k.out_kind = OUT_ACT;
     k.cpc = 4; k.nch = 1; k.lds_bytes = C::LDS;
     k.wbytes = C::WBYTES;
-    k.persistent = 1;
-    k.part_rows = 1;
     k.korder = 0;  // column-8 packing: 16x16x16 fragments over kernel-row quads (pack_ws9_weights)
-    k.launch = &launch;
     return k;
   }
 };

@@ -1,5 +1,6 @@
-// conv_ws_common.h — pieces shared by the weight-stationary persistent convs (conv_wstat.hip,
-// conv_wphase.hip): unit-fill kinds and the wait / barrier statements their LDS-DMA staging needs.
+// conv_ws_common.h — pieces shared by the weight-stationary persistent convs (conv_wst16.hip, conv_wphase.hip,
+// conv_ws2.hip, conv_ws9.hip, conv_ws1s.hip) and conv_gemm.hip: scalar f32x4 arithmetic, the tied-accumulator MFMA
+// forms, unit-fill kinds and the wait / barrier statements their LDS-DMA staging needs.
 #pragma once
 #include "conv_impl.h"
 

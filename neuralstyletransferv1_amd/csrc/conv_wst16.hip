@@ -1,15 +1,16 @@
 // conv_wst16.hip — weight-stationary residual-trunk conv on 16x16x32 MFMAs, one wave per SIMD.
 //
-// conv_wst32.hip's design (4 waves, each holding 32 output channels x 1152 K of weights for the whole launch in 256
-// AGPRs + 32 VGPRs; tiles of TH rows x 32 pixels; LDS-DMA staged fill cut into per-MFMA micro-steps) on the MFMA
-// shape that costs less energy per FLOP: the residual trunk runs at the board's power limit, and
-// bare bf16 loops deliver ~1.12-1.15x the FLOP/s on v_mfma_f32_16x16x32 than on 32x32x16 at equal cycles per FLOP
-// (MI355X_MICROARCH 'DVFS give-back' (7)).  Same layer and fusions (transformer_net.py:57-76 res1..res5,
+// 4 waves, each holding 32 output channels x 1152 K of weights for the whole launch in 256 AGPRs + 32 VGPRs; tiles of
+// TH rows x 32 pixels; LDS-DMA staged fill cut into per-MFMA micro-steps (first built on 32x32x16 MFMAs, a retired
+// design: DESIGN.md "Residual trunk"), on the MFMA shape that costs less energy per FLOP: the residual trunk runs
+// at the board's power limit, and bare bf16 loops deliver ~1.12-1.15x the FLOP/s on
+// v_mfma_f32_16x16x32 than on 32x32x16 at equal cycles per FLOP (MI355X_MICROARCH 'DVFS give-back' (7)).  Same layer and fusions (transformer_net.py:57-76 res1..res5,
 // transformer_net_nst.py:28-43): the producer's InstanceNorm apply + ReLU or the residual join in the fill, this
 // layer's InstanceNorm partial sums in the epilogue.
 //
 //   * each wave's 32 channels are two 16-row A blocks; a B read is 32 K x 16 pixels (half a tile row) and feeds both
-//     blocks for every y-tap (up to six MFMAs), so LDS reads per FLOP stay half of conv_wstat.hip's.
+//     blocks for every y-tap (up to six MFMAs), so LDS reads per FLOP are half of the retired 8-wave kernel's
+//     (DESIGN.md "Retired design").
 //   * an MFMA holds the SIMD's issue for 8 of its 16 cycles: the fill's micro-steps are one to three instructions
 //     each, one after each MFMA (288 MFMAs per part).
 //   * halo entry stride 288 B (18 x 16 B): the 16 pixels x 4 K-groups of a B read land on 16 distinct 4-bank slots
@@ -17,8 +18,6 @@
 //   * epilogue: bias, packing, v_permlane16_swap pairs (pixel halves) into 16-byte stores, the IN partial sums
 //     reduced over each 16-lane row.
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 
 #include "conv_ws_common.h"
 
@@ -26,8 +25,8 @@ namespace nst {
 
 constexpr uint32_t OOB = 0xFFFFFF00u;  // buffer offset past every launch's records: loads 0, stores dropped
 // cache policy of the output and residual-stream stores (32- / 64-byte pieces at the pixel stride, not whole lines):
-// default.  The streaming (nt) policy that suits conv_wstat.hip's whole-line stores made this kernel's epilogue
-// 3.6x slower (4.8k -> 17.5k cycles per tile, tools/w32_stamps.py)
+// default.  The streaming (nt) policy that suits whole-line stores (the retired 8-wave kernel's) made
+// this kernel's epilogue 3.6x slower (4.8k -> 17.5k cycles per tile, tools/w32_stamps.py)
 #ifndef NST_W32_ST
 #define NST_W32_ST 0
 #endif
@@ -37,10 +36,6 @@ constexpr uint32_t OOB = 0xFFFFFF00u;  // buffer offset past every launch's reco
 // own (nst_debug_w16_stamps): [0..3] parts, [4] epilogue, [5] loop head, [6] tiles
 #ifndef NST_WST32_STAMP
 #define NST_WST32_STAMP 0
-#endif
-// experiment builds (tools/gpu_stamps.sh): only the bf16 reflection-padded Johnson trunk variants (a third of the compile)
-#ifndef NST_W32_MIN
-#define NST_W32_MIN 0
 #endif
 #if NST_WST32_STAMP
 constexpr int STAMP_IT = 1, STAMP_PT = 16;
@@ -545,44 +540,17 @@ __global__ __launch_bounds__(256) void wst16_kernel(ConvParams p) {
 template <typename T, int TH, bool RES>
 struct Wst16Inst {
   using C = W16Cfg<TH, RES ? WF_RES : WF_NORM>;
-  static int cus() {
-    static const int v = [] {
-      int dev = 0, c = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        c = 256;
-      return c;
-    }();
-    return v;
-  }
   template <int FILL, bool ZPAD, bool XO = false>
   static void go(const ConvParams& p, int nb, hipStream_t st) {
     hipLaunchKernelGGL((wst16_kernel<T, TH, FILL, ZPAD, XO>), dim3(nb), dim3(C::NT), 0, st, p);
   }
+  // grid.x = tiles per frame, grid.y = frames; chunks of <= NFMAX frames per launch, every frame's records below
+  // the OOB offset; one workgroup per CU
   static void launch(const ConvParams& p0, dim3 grid, hipStream_t st) {
-    const int ntile = (int)grid.x, n = (int)grid.y;
     const size_t fin = (size_t)p0.hs * p0.ws * p0.cs * 2, fout = (size_t)p0.oh * p0.ow * p0.cout_stride * 2;
-    const int fmax = (int)std::min<size_t>(C::NFMAX, (size_t)OOB / std::max(fin, fout));
-    if (fmax < 1) return;
-    for (int f0 = 0; f0 < n; f0 += fmax) {
-      const int nf = std::min(fmax, n - f0);
-      ConvParams p = p0;
-      p.in = (const char*)p0.in + f0 * fin;
-      p.out = (char*)p0.out + f0 * fout;
-      if (p0.res_r) p.res_r = (const char*)p0.res_r + f0 * fin;
-      if (p0.res_out) p.res_out = (char*)p0.res_out + f0 * fin;
-      if (p0.in_norm) p.in_norm = p0.in_norm + (size_t)f0 * p0.cs;
-      p.partial = p0.partial + (size_t)f0 * ntile * p0.cout_stride * 2;
-      p.n_work = nf * ntile;
-      const int nb = capped_blocks(std::min(p.n_work, cus()));
-      note_launch(nb, p.n_work);
+    launch_frame_chunks(p0, (int)grid.x, (int)grid.y, C::NFMAX, (size_t)OOB / std::max(fin, fout), 1, device_cus(),
+                        [st](const ConvParams& p, int nb) {
       const bool zp = p.axis_mode != AX_REFLECT;
-#if NST_W32_MIN
-      // experiment build: the Johnson trunk's three variants only (reflection padding)
-      if (zp) return;
-      if constexpr (RES) go<WF_RES, false>(p, nb, st);
-      else if (p.res_out != nullptr) go<WF_NORM, false, true>(p, nb, st);
-      else go<WF_NORM, false>(p, nb, st);
-#else
       if constexpr (RES) {
         zp ? go<WF_RES, true>(p, nb, st) : go<WF_RES, false>(p, nb, st);
       } else {
@@ -593,22 +561,14 @@ struct Wst16Inst {
         else
           zp ? go<WF_RAW, true>(p, nb, st) : go<WF_RAW, false>(p, nb, st);
       }
-#endif
-    }
+    });
   }
   static ConvKernelInfo info() {
-    ConvKernelInfo k;
-    std::memset(&k, 0, sizeof(k));
-    k.dtype = dtype_code<T>();
-    k.mode = MODE_WSTAT;
+    ConvKernelInfo k = conv_info(dtype_code<T>(), MODE_WSTAT, &launch);
     k.ks = 3; k.stride = 1; k.cinp = C::CINP; k.bn = 128; k.th = TH; k.tw = C::TW; k.wm = C::NW; k.wn = 2;  // wn = 2: two 16-channel blocks per wave (pack_wst16_weights)
-    k.in_kind = IN_ACT; k.out_kind = OUT_ACT;
     k.cpc = 8; k.nch = 16; k.lds_bytes = C::LDS;
     k.wbytes = C::NW * C::NKS * 1024;
-    k.persistent = 1;
-    k.part_rows = 1;
     k.res = RES ? 1 : 0;
-    k.launch = &launch;
     return k;
   }
 };
@@ -653,18 +613,15 @@ W16_INST(W16_T_, WF_RES, true, false)
 W16_KERNELS(W16_EXTERN, __bf16)
 W16_KERNELS(W16_EXTERN, _Float16)
 #endif
-// searched before conv_table_wstat (first match wins); NST_WST16=0 in the environment hides it (A/B runs)
+// the residual trunk's table (nst_api.cpp find_conv_kernel: first match wins; no_wstat deselects it)
 const ConvKernelInfo* conv_table_wst16(int* count) {
   static const ConvKernelInfo table[] = {
       Wst16Inst<__bf16, NST_WST16_TH, false>::info(),  // residual trunk
       Wst16Inst<__bf16, NST_WST16_TH, true>::info(),   // + residual join in the fill
-#if !NST_W32_MIN
       Wst16Inst<_Float16, NST_WST16_TH, false>::info(),  // fp16 mode
       Wst16Inst<_Float16, NST_WST16_TH, true>::info(),
-#endif
   };
-  const char* env = std::getenv("NST_WST16");
-  *count = (env != nullptr && env[0] == '0') ? 0 : (int)(sizeof(table) / sizeof(table[0]));
+  *count = (int)(sizeof(table) / sizeof(table[0]));
   return table;
 }
 #endif

@@ -66,7 +66,7 @@ const ConvKernelInfo* find_conv_kernel(int dtype, int mode, int ks, int stride, 
                                        int out_kind, int res, bool no_persistent) {
   typedef const ConvKernelInfo* (*TableFn)(int*);
   // 16-bit formats (bf16, fp16) share the specialised tables; an entry matches only its own dtype
-  // (conv_table_bf16_wl first: no_persistent skips it, and only it)
+  // no_persistent skips the generic kernel's persistent form (MODE_STD entries that walk: conv_table_bf16_wl's)
   const TableFn tables_16[] = {conv_table_bf16_wl, conv_table_wst16, conv_table_wphase, conv_table_ws2, conv_table_ws9,
                                conv_table_out9, conv_table_bf16, conv_table_f16, conv_table_ws1s};
   // 4-byte activation formats (fp32, split-fp16): the generic kernels, and the split-fp16 row-streaming output conv
@@ -74,11 +74,12 @@ const ConvKernelInfo* find_conv_kernel(int dtype, int mode, int ks, int stride, 
   const bool h16 = !f32_storage(dtype);
   const TableFn* tables = h16 ? tables_16 : tables_f32;
   const int ntables = (int)(h16 ? std::size(tables_16) : std::size(tables_f32));
-  for (int ti = (h16 && no_persistent) ? 1 : 0; ti < ntables; ++ti) {
+  for (int ti = 0; ti < ntables; ++ti) {
     int count = 0;
     const ConvKernelInfo* t = tables[ti](&count);
     for (int i = 0; i < count; ++i) {
       const ConvKernelInfo& k = t[i];
+      if (no_persistent && k.mode == MODE_STD && k.persistent) continue;
       if (k.dtype == dtype && k.mode == mode && k.ks == ks && k.stride == stride && k.cinp == cinp && k.bn == bn &&
           k.in_kind == in_kind && k.out_kind == out_kind && k.res == res)
         return &k;

@@ -12,7 +12,8 @@ columns with a ragged last column and a ragged last row in every kernel of its p
      the recorded grids prove the walk (n_work > blocks per kernel family);
   b. walk invariance: caps 1, 2, 5, 8, 16 give the uncapped run's outputs and captured buffers bit for bit;
   c. frame chunks (8 + 1 frames of the joined trunk conv) inside a two-workgroup walk;
-  d. refusals and reset.
+  d. refusals and reset;
+  f. the uncapped grid where the work exceeds the resident workgroups (8x360x640): CUs x each launcher's multiplier.
 (e, the cap arithmetic without a GPU, is tests/test_host.py::test_capped_blocks.)
 
 conv_out9 is no walk (one work item per wave); the cap reaches its slot count instead, so the number of row segments
@@ -238,6 +239,57 @@ def test_stream_split_sees_the_cap():
     assert len(walking) == 15
     for g, k in walking:
         assert g["launches"] == 1 and g["blocks"] == 2 and g["n_work"] * n == k and g["n_work"] > 2, (g, k)
+
+
+# Workgroups per CU of each walking op's uncapped grid (blocks = CUs x k once the work exceeds it), by layer name.
+# Recorded from a run of test_resident_grids on the commit before the launchers moved onto csrc/conv_launch.h, and
+# cross-checked against the launchers' own arithmetic: conv_ws9 8 / NW = 2 (four-wave workgroups); conv_ws2
+# OCC * 4 / NW per instantiation (bf16 32 -> 64: 4 * 4 / 8 = 2; 64 -> 128: 2 * 4 / 8 = 1; ReCoNet's 64 -> 96:
+# 3 * 4 / 12 = 1; the split-precision ones: 2 * 4 / 8 = 1); conv_wst16, conv_wphase and conv_ws1s one workgroup per
+# CU; the generic persistent kernel its occupancy (one 512-thread workgroup per CU: its LDS weight ring).
+_TRUNK = [f"res{i}.conv{j}.conv2d" for i in range(1, 6) for j in (1, 2)]
+_JOHNSON_K = {"conv1.conv2d": 2, "conv2.conv2d": 2, "conv3.conv2d": 1, **{name: 1 for name in _TRUNK},
+              "deconv1.conv2d": 1, "deconv2.conv2d": 1}
+RESIDENT_K = {
+    ("johnson", "bf16", ()): _JOHNSON_K,
+    ("johnson", "fp16m", ()): {**_JOHNSON_K, "conv2.conv2d": 1},  # the split-operand conv2: OCC 2
+    ("johnson", "bf16", ("no_wstat",)): _JOHNSON_K,               # the trunk on the generic persistent kernel
+    # conv_ws9 (48 channels padded to 64), the narrow-input conv_ws2 (64 -> 96), conv_wphase (96 -> 48)
+    ("reconet", "bf16", ()): {"encoder.layers.0.layers.0.layers.1": 2, "encoder.layers.1.layers.0.layers.1": 1,
+                              "decoder.layers.3.layers.0.layers.1": 1},
+}
+RESIDENT_SHAPE = (8, 360, 640)  # johnson's trunk: a 90x160 map in 8x32 tiles, 12 * 5 * 8 = 480 work items on 256 CUs
+
+
+@pytest.mark.parametrize("arch,dtype,ksel", list(RESIDENT_K),
+                         ids=lambda v: ("-".join(v) or "default") if isinstance(v, tuple) else None)
+def test_resident_grids(arch, dtype, ksel):
+    """The uncapped grid once the work exceeds the resident slots: CUs x the launcher's workgroups per CU (RESIDENT_K),
+    for every walking op of the net.  The small shapes above never reach it (blocks = n_work there), and a slip in it,
+    such as conv_ws9 losing its x2, changes speed and nothing else.  8 x 360 x 640 is the smallest batch of the common
+    frame sizes at which every walking op of these nets has more work items than resident workgroups."""
+    n, h, w = RESIDENT_SHAPE
+    eng = _net(arch, dtype, ksel=ksel).engine()
+    x = torch.from_numpy(_frames(n, h, w)).to(eng.device)
+    eng.stylize_u8(x, SHAPES[arch][3])
+    torch.cuda.synchronize()
+    cus = torch.cuda.get_device_properties(eng.device).multi_processor_count
+    names = eng.layer_names()
+    want = RESIDENT_K[(arch, dtype, ksel)]
+    seen = {}
+    for d, g in zip(eng.op_descs(n, h, w), eng.op_grids()):
+        if g["launches"] and d["kernel_mode"] != 3:  # conv_out9 reports its grid too, and does not walk
+            print(names[d["layer"]], "mode", d["kernel_mode"], "kdt", d["kernel_dtype"], g, "CUs", cus)
+            seen[names[d["layer"]]] = (d["kernel_mode"], g)
+    assert set(seen) == set(want), (sorted(seen), sorted(want))
+    for name, (mode, g) in seen.items():
+        assert mode in WALK_MODES + (0,), (name, mode)
+        for blocks, n_work in g["per_launch"]:
+            assert n_work > blocks and blocks == cus * want[name], (name, mode, g, cus, want[name])
+    modes = {m for m, _ in seen.values()}
+    if arch == "johnson":
+        assert {5, 6, 7} <= modes and ((4 in modes) == (not ksel)) and ((0 in modes) == bool(ksel)) and \
+            ((8 in modes) == (dtype == "fp16m")), modes
 
 
 def test_refusals_and_reset():
