@@ -777,6 +777,56 @@ typedef struct nst_multi_model_frame {
 int nst_multi_model_frames(const uint8_t* bank, int n_bank, int h, int w, const nst_multi_model_frame* frames, int n,
                            uint8_t* out, void* stream);
 
+/* ---- Soft-blob compositor: create_soft_multi_blob_masks and the frame loop of scripts/selfstyle_blob.py
+ * (generate_blob_video :295-474; the same masks in scripts/morph_faces.py and scripts/gen_pytorch_only_videos.py;
+ * selfstyle_blob.py here) ----
+ * The masks are the reference's numpy code under the NumPy it pins (< 2.0): every array operation float32, every Python
+ * scalar rounded to fp32 once before it meets the array (the host does that when it fills the structs).  For blob b of
+ * n_blobs, octave o = 0..3, pixel (y, x), each operation rounded to fp32 alone, no contraction, sinf / expf the accurate
+ * library functions, both divisions IEEE:
+ *   r  = amp[o]      * sinf((((yn[y] * freq[o]) * pi32 + phase_y[b][o]) + t_y[o]) + blob_phase[b])
+ *   c  = amp[o]      * sinf((((xn[x] * freq[o]) * pi32 + phase_x[b][o]) + t_x[o]) + blob_phase[b])
+ *   d  = amp_half[o] * sinf(((((xn[x] + yn[y]) * freq[o]) * pi32 + phase_t[b][o]) + t_t) + blob_phase[b])
+ *   noise_b = ((noise_b + r) + c) + d   over o = 0..3 in that order, from 0
+ *   m = max_b noise_b;  e_b = expf((noise_b - m) / T);  s = e_0 + e_1 + ... in blob order;  w_b = e_b / (s + 1e-6f)
+ * yn[h], xn[w]: fp32 device tables, np.linspace(0, 1, h or w, dtype=float32).  r and c are evaluated once per row and
+ * column of the block a workgroup owns, d once per pixel, octave and blob.
+ * nst_blob_frames: n output frames [n,h,w,3] u8 RGB from a bank of u8 RGB images [n_bank,h,w,3] (device; any alignment)
+ * and a host table of n per-frame descriptors; any n >= 1, the call splits it into launches itself.  Per channel:
+ *   I_b = cv2.addWeighted(bank[lo_b], w_lo_b, bank[hi_b], w_hi_b, 0)      u8, rounded half to even, as nst_morph_frames
+ *   F = 0;  for b = 0..n_blobs-1:  F = F + (float)I_b * w_b;   out = (uint8)F   truncated
+ * nst_blob_masks: the weights alone, fp32 [n,n_blobs,h,w] (device), from the same field and descriptors (the four
+ * still fields of a blob are not read).
+ * NST_E_INVALID: n < 1, n_bank < 1, a null pointer, n_blobs outside 1..NST_BLOB_MAX, T not finite or <= 0, lo or hi of
+ * a blob b < n_blobs outside 0..n_bank-1, out overlapping the bank; NST_E_SHAPE: h or w outside 1..32768.  Everything is
+ * checked before the first launch. */
+#define NST_BLOB_MAX 8
+typedef struct nst_blob_field { /* what a video keeps for all of its frames */
+  int n_blobs;
+  float T; /* max(0.1, feather * 5) */
+  float freq[4], amp[4], amp_half[4];
+  float phase_y[NST_BLOB_MAX][4], phase_x[NST_BLOB_MAX][4], phase_t[NST_BLOB_MAX][4];
+  float blob_phase[NST_BLOB_MAX];
+} nst_blob_field;
+typedef struct nst_blob_still { /* a blob's image: the cross-fade of two neighbouring stills of its stream */
+  int lo, hi;
+  float w_lo, w_hi;
+} nst_blob_still;
+typedef struct nst_blob_frame {
+  float t_y[4], t_x[4], t_t; /* time_offset * (1 + 0.3 o), * (1.2 + 0.2 o), * 1.5 */
+  nst_blob_still blob[NST_BLOB_MAX];
+} nst_blob_frame;
+int nst_blob_frames(const uint8_t* bank, int n_bank, int h, int w, const float* yn, const float* xn,
+                    const nst_blob_field* field, const nst_blob_frame* frames, int n, uint8_t* out, void* stream);
+int nst_blob_masks(int h, int w, const float* yn, const float* xn, const nst_blob_field* field,
+                   const nst_blob_frame* frames, int n, float* out, void* stream);
+
+/* cv2.addWeighted(a, wa, b, wb, 0) on two u8 device buffers of n_bytes bytes (any alignment): per byte in fp32
+ * saturate(rint_half_even((float)a * (float)wa + (float)b * (float)wb)), each weight rounded to fp32 once.
+ * NST_E_INVALID: a null pointer, n_bytes < 1, out overlapping a or b. */
+int nst_add_weighted_u8(const uint8_t* a, double wa, const uint8_t* b, double wb, size_t n_bytes, uint8_t* out,
+                        void* stream);
+
 /* ---- PNG encode on the owner rank (pipeline.py:2099-2119 `Image.fromarray(out).save(path)`, the reference's
  * default --image_ext png at :2170) ----
  * n u8 frames [n,h,w,c] (c = 1 grey, 3 RGB, 4 RGBA; device) -> n complete PNG files, file j at out + j*out_stride,

@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "nst_camera_pulse_u8", "nst_camera_rect_subpix_u8", "nst_camera_lanczos_u8", "nst_camera_hue_u8",
     "nst_camera_smooth_u8", "nst_camera_scratch_bytes", "nst_camera_frames_u8",
     "nst_style_morph_frames", "nst_multi_model_frames",
+    "nst_blob_frames", "nst_blob_masks", "nst_add_weighted_u8",
     "nst_set_grid_cap", "nst_capped_blocks", "nst_op_last_grid", "nst_op_launch_grid",
 )
 NST_FLOW_GAUSSIAN = 256  # cv2.OPTFLOW_FARNEBACK_GAUSSIAN (nst_flow_farneback_ex flags)
@@ -70,6 +71,7 @@ NST_CAMERA_MAX_FRAMES, NST_CAMERA_MAX_SMOOTH = 32, 15  # frames per nst_camera_*
 NST_STYLE_MORPH_MAX_STYLES = 8  # ladder families per side of an nst_style_morph_frames descriptor
 NST_SM_FILTER_NONE, NST_SM_FILTER_SAT, NST_SM_FILTER_VIBRANCE, NST_SM_FILTER_WARM = 0, 1, 2, 3
 NST_MM_NONE, NST_MM_PLAIN, NST_MM_STYLED = 0, 1, 2  # base / cross kinds of an nst_multi_model_frames descriptor
+NST_BLOB_MAX = 8  # blobs of an nst_blob_frames / nst_blob_masks field
 NST_E_INVALID, NST_E_SHAPE, NST_E_WORKSPACE, NST_E_DATA = -1, -3, -5, -7
 NST_JPEG_444, NST_JPEG_422, NST_JPEG_420 = 0, 1, 2
 # region compositor limits / geometry kinds (include/nst_hip.h NST_REGION_*, NST_RG_*)
@@ -138,6 +140,24 @@ class NstMultiModelFrame(ctypes.Structure):
                 ("sat_on", ctypes.c_int), ("sat", ctypes.c_float), ("fin", ctypes.c_int),
                 ("fin_w", ctypes.c_float * 2), ("cross_kind", ctypes.c_int), ("next", NstMultiModelStill),
                 ("cross_w", ctypes.c_float * 2)]
+
+
+class NstBlobField(ctypes.Structure):
+    """nst_blob_field: what a blob video keeps for all of its frames (include/nst_hip.h "Soft-blob compositor")."""
+    _fields_ = [("n_blobs", ctypes.c_int), ("T", ctypes.c_float), ("freq", ctypes.c_float * 4),
+                ("amp", ctypes.c_float * 4), ("amp_half", ctypes.c_float * 4),
+                ("phase_y", (ctypes.c_float * 4) * NST_BLOB_MAX), ("phase_x", (ctypes.c_float * 4) * NST_BLOB_MAX),
+                ("phase_t", (ctypes.c_float * 4) * NST_BLOB_MAX), ("blob_phase", ctypes.c_float * NST_BLOB_MAX)]
+
+
+class NstBlobStill(ctypes.Structure):
+    _fields_ = [("lo", ctypes.c_int), ("hi", ctypes.c_int), ("w_lo", ctypes.c_float), ("w_hi", ctypes.c_float)]
+
+
+class NstBlobFrame(ctypes.Structure):
+    """nst_blob_frame: one output frame's time terms and, per blob, the cross-fade of two stills."""
+    _fields_ = [("t_y", ctypes.c_float * 4), ("t_x", ctypes.c_float * 4), ("t_t", ctypes.c_float),
+                ("blob", NstBlobStill * NST_BLOB_MAX)]
 
 
 _lib = None
@@ -330,6 +350,12 @@ def lib() -> ctypes.CDLL:
         L.nst_style_morph_frames.restype = i
         L.nst_multi_model_frames.argtypes = [vp, i, i, i, ctypes.POINTER(NstMultiModelFrame), i, vp, vp]
         L.nst_multi_model_frames.restype = i
+        pbf, pbd = ctypes.POINTER(NstBlobField), ctypes.POINTER(NstBlobFrame)
+        L.nst_blob_frames.argtypes = [vp, i, i, i, vp, vp, pbf, pbd, i, vp, vp]
+        L.nst_blob_masks.argtypes = [i, i, vp, vp, pbf, pbd, i, vp, vp]
+        L.nst_add_weighted_u8.argtypes = [vp, dbl, vp, dbl, sz, vp, vp]
+        for name in ("nst_blob_frames", "nst_blob_masks", "nst_add_weighted_u8"):
+            getattr(L, name).restype = i
         for name in ("nst_png_bound", "nst_png_workspace_bytes", "nst_png_encode_u8"):
             getattr(L, name).restype = i
         for name in ("nst_lab_planes_u8", "nst_lab_ema_planes", "nst_lab_merge_u8", "nst_input_exact"):

@@ -6,8 +6,8 @@
 //   * morph_v2's flow post-processing: GaussianBlur((15, 15), 3.0) of each component, then the radial term where
 //     the blurred flow is shorter than 2 px;
 //   * every frame of a transition in one launch: two cv2.remap(INTER_LINEAR, BORDER_REFLECT) warps in OpenCV's
-//     1/32-pixel fixed point and cv2.addWeighted, per pixel over all k frames; the run of pixels a thread owns and its
-//     store are the compositor core's (u8run_common.h).
+//     1/32-pixel fixed point and cv2.addWeighted, per pixel over all k frames; the run of pixels a thread owns, its
+//     store and add_weighted are the compositor core's (u8run_common.h).
 // cv2 is not installed here: all of it is restated from OpenCV's sources and the scripts, parity unpinned.  The
 // translation unit is built with -ffp-contract=off: every fp32 product and sum rounds on its own, in the order written.
 #include <math.h>
@@ -159,12 +159,6 @@ __device__ __forceinline__ void remap_reflect(const uint8_t* __restrict__ img, i
 #pragma unroll
   for (int c = 0; c < 3; ++c)
     rgb[c] = (w00 * (int)p00[c] + w01 * (int)p01[c] + w10 * (int)p10[c] + w11 * (int)p11[c] + 16384) >> 15;
-}
-
-// cv2.addWeighted on 8-bit images: saturate(rint_half_even(p1 * wa + p2 * wb)) in fp32
-__device__ __forceinline__ uint32_t add_weighted(int p1, int p2, float wa, float wb) {
-  const float v = (float)p1 * wa + (float)p2 * wb;
-  return (uint32_t)fminf(fmaxf(rintf(v), 0.f), 255.f);
 }
 
 // Each thread owns one run of U8_RUN consecutive pixels (u8run_common.h), loads their forward and backward flow

@@ -1,5 +1,5 @@
 // u8run_common.h — what the u8 frame compositors share (morph_frames_kernel, camera_out_kernel, style_morph_kernel,
-// multi_model_kernel and their entry points; DESIGN.md §7.4 "The compositor core").
+// multi_model_kernel, blob_frames_kernel and their entry points; DESIGN.md §7.4 "The compositor core").
 // Device: each thread owns U8_RUN consecutive pixels (12 bytes) of the flattened RGB frame.  A run of a source image
 // is loaded as three dwords (RunRaw), the 12 result bytes leave through store_run.  VEC: every image and every run
 // starts on a dword boundary (h*w a multiple of 4, the buffers 4-byte aligned), so every run is whole and moves as
@@ -61,6 +61,12 @@ __device__ __forceinline__ int clip_u8(float v) { return (int)fminf(fmaxf(v, 0.f
 // the same value kept as a float (what .astype(np.float32) then gives)
 __device__ __forceinline__ float trunc_u8f(float v) { return truncf(fminf(fmaxf(v, 0.f), 255.f)); }
 
+// cv2.addWeighted on 8-bit images: saturate(rint_half_even(p1 * wa + p2 * wb)) in fp32
+__device__ __forceinline__ uint32_t add_weighted(int p1, int p2, float wa, float wb) {
+  const float v = (float)p1 * wa + (float)p2 * wb;
+  return (uint32_t)fminf(fmaxf(rintf(v), 0.f), 255.f);
+}
+
 // a run's 12 result bytes, each 0..255 in a register of its own
 struct RunBytes {
   uint32_t b[U8_RUN_BYTES];
@@ -108,6 +114,16 @@ inline int bank_call_refused(const std::string& who, const void* bank, int n_ban
 
 inline bool bad_index(int i, int n_bank) { return i < 0 || i >= n_bank; }
 
+// the last refusal of a bank call: n output frames of fbytes bytes may not overlap the bank
+inline bool out_overlaps_bank(const std::string& who, const uint8_t* bank, int n_bank, size_t fbytes, const uint8_t* out,
+                              int n) {
+  const uint8_t* bank_end = bank + (size_t)n_bank * fbytes;
+  const uint8_t* out_end = out + (size_t)n * fbytes;
+  if (!(out < bank_end && bank < out_end)) return false;
+  set_error(who + ": out overlaps the bank");
+  return true;
+}
+
 // The descriptors travel by value, the frame is blockIdx.z of the launch's group: BANK_GROUP of them fit the 4 KB
 // argument block.
 constexpr int BANK_GROUP = 8;
@@ -126,12 +142,7 @@ int launch_bank_frames(const std::string& who, const char* what, BankKernel<Fram
                        const Frame* frames, int n, uint8_t* out, void* stream) {
   static_assert(sizeof(BankBatch<Frame>) + 64 <= 4096, "the descriptors of one launch must fit the kernel-argument block");
   const size_t hw = (size_t)h * w, fbytes = hw * 3;
-  const uint8_t* bank_end = bank + (size_t)n_bank * fbytes;
-  const uint8_t* out_end = out + (size_t)n * fbytes;
-  if (out < bank_end && bank < out_end) {
-    set_error(who + ": out overlaps the bank");
-    return NST_E_INVALID;
-  }
+  if (out_overlaps_bank(who, bank, n_bank, fbytes, out, n)) return NST_E_INVALID;
   const bool vec = (hw % 4) == 0 && ((uintptr_t)bank & 3) == 0 && ((uintptr_t)out & 3) == 0;
   const size_t threads = (hw + U8_RUN - 1) / U8_RUN;
   for (int first = 0; first < n; first += BANK_GROUP) {

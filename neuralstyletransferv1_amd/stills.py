@@ -1,4 +1,4 @@
-"""What the still compositors' CLIs (morph, style_morph, multi_model_video) share around their kernels: the output
+"""What the still compositors' CLIs (morph, style_morph, multi_model_video, selfstyle_blob) share around their kernels: the output
 flags and the numbered-file writer, the close of a run, the two easing curves, the ctypes call of a bank kernel
 (csrc/u8run_common.h, launch_bank_frames) and the loader of a bank of stills.
 
@@ -106,9 +106,11 @@ def close_run(tag: str, wr: FrameWriter, fps, video: Optional[str]) -> None:
 
 
 # ---- device ----
-def bank_frames(who: str, entry: str, pack: Callable, bank_u8: torch.Tensor, descs: Sequence[dict]) -> torch.Tensor:
+def bank_frames(who: str, entry: str, pack: Callable, bank_u8: torch.Tensor, descs: Sequence[dict],
+                extra: Sequence = ()) -> torch.Tensor:
     """A bank call: bank uint8 [n_bank,h,w,3] on the device and the plan's descriptors -> uint8 [n,h,w,3] through the
-    C entry point `entry`, the descriptors packed by pack(); `who` is the calling wrapper's name in the messages."""
+    C entry point `entry`, the descriptors packed by pack(); `who` is the calling wrapper's name in the messages.
+    `extra`: what the entry point takes between w and the descriptors (nst_blob_frames: its tables and its field)."""
     _lib.require_gpu_tensor(bank_u8, f"{who} bank")
     if bank_u8.dtype != torch.uint8 or bank_u8.dim() != 4 or bank_u8.shape[3] != 3:
         raise NstError(f"{who}: expected a uint8 [n_bank,h,w,3] bank, got {bank_u8.dtype} {tuple(bank_u8.shape)}")
@@ -116,7 +118,7 @@ def bank_frames(who: str, entry: str, pack: Callable, bank_u8: torch.Tensor, des
     n_bank, h, w, _ = bank.shape
     n = len(descs)
     out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=bank.device)
-    check(getattr(lib(), entry)(bank.data_ptr(), n_bank, h, w, pack(descs), n, out.data_ptr(),
+    check(getattr(lib(), entry)(bank.data_ptr(), n_bank, h, w, *extra, pack(descs), n, out.data_ptr(),
                                 _lib.stream_ptr(bank.device)), entry)
     bank.record_stream(torch.cuda.current_stream(bank.device))
     return out
