@@ -50,7 +50,9 @@ from datetime import timedelta
 from pathlib import Path
 from typing import Dict, List, Optional
 
-import numpy as np
+from . import frame_loop
+# the frame loop's parts live in frame_loop.py; these names stay this module's too (tests, tools, regions.py)
+from .frame_loop import FrameSource, _get_image_with_exif_pil, _log, load_mask_fit, load_mask_u8, parse_wh  # noqa: F401
 
 IO_PRESETS_AUTO = {  # pipeline.py:2518-2523
     "transformer": "imagenet_255",
@@ -64,10 +66,6 @@ SLOTS = ["b", "c", "d", "e", "f", "g", "h"]
 # the last style_frames run on this process: frames, seconds of the frame loop (decode -> GPU -> encode, from the
 # first frame load to the last file written) and seconds of setup before it (model load, plans, size scan)
 LAST_RUN_STATS: Dict[str, float] = {}
-
-
-def _log(msg: str) -> None:
-    print(msg, flush=True)
 
 
 # ----------------------------------------------------------------------------- argparse
@@ -221,23 +219,6 @@ def reject_out_of_scope(args) -> None:
 
 
 # ----------------------------------------------------------------------------- host I/O helpers
-# EXIF Orientation (tag 0x0112) -> counter-clockwise PIL rotation that uprights the image
-_EXIF_UPRIGHT = {3: 180, 6: 270, 8: 90}
-
-
-def _get_image_with_exif_pil(image_path: str):
-    """EXIF-normalised RGB image (pipeline.py:171-187: orientations 3/6/8 rotated upright, others
-    untouched; JPEG's legacy _getexif table, absent on other formats)."""
-    from PIL import Image
-    img = Image.open(image_path)
-    tags = getattr(img, "_getexif", lambda: None)() or {}
-    angle = _EXIF_UPRIGHT.get(tags.get(0x0112))
-    if angle is not None:
-        img = img.rotate(angle, expand=True)
-    img.load()
-    return img if img.mode == "RGB" else img.convert("RGB")  # (convert of an RGB image is a copy)
-
-
 def sh(cmd: str, check=True):
     _log(f"$ {cmd}")
     r = subprocess.run(cmd, shell=True)
@@ -319,48 +300,6 @@ def lab_weights_rest(weights_str: Optional[str], num_models: int) -> List[float]
     return [1.0 / max(num_models - 1, 1)] * max(num_models - 1, 1)
 
 
-def _pct_to_px(pct: float, H: int) -> int:
-    """pipeline.py:278-282."""
-    try:
-        return int(round(max(0.0, float(pct)) * 0.01 * H))
-    except Exception:
-        return 0
-
-
-def load_mask_fit(mask_path: str, target_hw, invert: bool, autofix: bool = True, force_transpose: bool = False) -> np.ndarray:
-    """pipeline.py:284-353 without feathering: float32 HxW alpha in [0,1] (host file decode + NEAREST fit)."""
-    return load_mask_u8(mask_path, target_hw, invert, autofix, force_transpose).astype(np.float32) / 255.0
-
-
-def load_mask_u8(mask_path: str, target_hw, invert: bool, autofix: bool = True, force_transpose: bool = False) -> np.ndarray:
-    """pipeline.py:292-347: the fitted (and optionally inverted) uint8 mask, before the feather."""
-    from PIL import Image
-    W_tgt, H_tgt = target_hw[1], target_hw[0]
-    m_img = Image.open(mask_path).convert("L")
-    mw, mh = m_img.size
-    if force_transpose:
-        m_img = m_img.transpose(Image.TRANSPOSE)
-        mw, mh = m_img.size
-    if autofix and (W_tgt != H_tgt):
-        reason = None
-        if (mw, mh) == (H_tgt, W_tgt):
-            reason = "exact-dimension swap"
-        else:
-            def _dist(a, b):
-                return abs(np.log(max(a, 1e-6)) - np.log(max(b, 1e-6)))
-            ar_tgt, ar_mask, ar_sw = float(W_tgt) / float(H_tgt), float(mw) / float(mh), float(H_tgt) / float(W_tgt)
-            if _dist(ar_mask, ar_sw) + 1e-6 < _dist(ar_mask, ar_tgt):
-                reason = "aspect-ratio closer to swapped"
-        if reason:
-            _log(f"[mask][autofix] {Path(mask_path).name}: {reason}; applying Image.TRANSPOSE")
-            m_img = m_img.transpose(Image.TRANSPOSE)
-    m_img = m_img.resize((W_tgt, H_tgt), Image.Resampling.NEAREST)
-    m = np.array(m_img, dtype=np.uint8)
-    if invert:
-        m = 255 - m
-    return m
-
-
 def _detect_transformer_type(checkpoint_path: str) -> str:
     """pipeline.py:72-79: NST_Train checkpoints have 'down1.' keys."""
     import torch
@@ -435,110 +374,9 @@ def load_model(path: str, model_type: str, device, dtype: str, slot: str = "A", 
     return model, arch
 
 
-# ----------------------------------------------------------------------------- the frame loop
-class FrameSource:
-    """Frames by index: files (PIL decode, optional --inference_res LANCZOS), --input_dir sources staged in memory
-    (`staged`: (source path, JPEG quality or None) per frame), or a synthetic stream."""
-
-    def __init__(self, files: Optional[List[Path]] = None, synthetic=None, infer_res: int = 0, staged=None):
-        self.files = files if files is not None else ([s for s, _ in staged] if staged is not None else None)
-        self.staged = staged
-        self.synthetic = synthetic  # (n, h, w)
-        self.infer_res = infer_res
-
-    def __len__(self):
-        return len(self.files) if self.files is not None else self.synthetic[0]
-
-    def size(self, i: int):
-        if self.files is None:
-            return (self.synthetic[1], self.synthetic[2])
-        from PIL import Image
-        with Image.open(self.files[i]) as im:
-            w, h = im.size
-            if self.staged is not None:  # the staged copy is EXIF-upright: orientations 6 / 8 swap the sides
-                try:
-                    tags = getattr(im, "_getexif", lambda: None)() or {}
-                except Exception:  # noqa: BLE001 -- unreadable EXIF: the raw copy is staged (_open_rgb)
-                    tags = {}
-                if _EXIF_UPRIGHT.get(tags.get(0x0112)) in (90, 270):
-                    w, h = h, w
-        return (h, w)
-
-    def _open_rgb(self, i: int):
-        from PIL import Image
-        if self.staged is None:
-            im = Image.open(self.files[i])
-            im.load()
-            return im if im.mode == "RGB" else im.convert("RGB")
-        # the reference's --input_dir staging (pipeline.py:2577-2586): EXIF-upright RGB, re-saved as the staged
-        # frame -- PNG (lossless: the decoded frame is that RGB image itself) or JPEG at --jpeg_quality, whose
-        # encode -> decode round trip runs here in memory (the same bytes PIL writes, so the same pixels)
-        src, q = self.staged[i]
-        try:
-            pil = _get_image_with_exif_pil(str(src))
-        except Exception as e:  # noqa: BLE001 -- pipeline.py:2587-2589: the raw file is copied instead
-            _log(f"[stage][WARN] EXIF-normalize failed for {src} ({e}); copying instead")
-            im = Image.open(src)
-            im.load()
-            return im if im.mode == "RGB" else im.convert("RGB")
-        if q is None:
-            return pil
-        # the round trip goes through an anonymous in-memory file with a real descriptor: Pillow encodes to a
-        # descriptor with the GIL released (to a BytesIO it holds the GIL, so a thread pool would serialise)
-        if not hasattr(os, "memfd_create"):  # (not Linux: same bytes through a BytesIO)
-            import io
-            buf = io.BytesIO()
-            pil.save(buf, format="JPEG", quality=q)
-            buf.seek(0)
-            im = Image.open(buf)
-            im.load()
-            return im if im.mode == "RGB" else im.convert("RGB")
-        with os.fdopen(os.memfd_create("nst_stage"), "w+b") as f:
-            pil.save(f, format="JPEG", quality=q)
-            f.seek(0)
-            im = Image.open(f)
-            im.load()
-            return im if im.mode == "RGB" else im.convert("RGB")
-
-    def load(self, i: int):
-        """-> (original uint8 HxWx3, model-input uint8 hxwx3)."""
-        if self.files is None:
-            from .synthetic import make_frames
-            f = make_frames(1, self.synthetic[1], self.synthetic[2], seed=10_000 + i)[0]
-            return f, f
-        from PIL import Image
-        pil_rgb = self._open_rgb(i)
-        pil_src = pil_rgb
-        if self.infer_res > 0:  # pipeline.py:1089-1097
-            w0, h0 = pil_rgb.size
-            m0 = max(w0, h0)
-            if m0 > self.infer_res:
-                r = self.infer_res / float(m0)
-                pil_src = pil_rgb.resize((int(round(w0 * r)), int(round(h0 * r))), Image.Resampling.LANCZOS)
-        a = np.asarray(pil_rgb, dtype=np.uint8)
-        return a, (a if pil_src is pil_rgb else np.asarray(pil_src, dtype=np.uint8))
-
-
-def style_frames(args, frames_dir: Optional[Path], model_path, output_prefix: str, image_ext_out: str, device_str: str,
-                 threads: int, stride: int, max_frames: Optional[int], smooth_lightness: bool, smooth_alpha: float,
-                 jpeg_quality: int, io_preset: str, smooth_chroma: bool = False, chroma_alpha: float = 0.85,
-                 blend: float = 1.0, image_mode: bool = False, save_map: Optional[Dict[int, str]] = None,
-                 rank: int = 0, world: int = 1):
-    """Same signature/behaviour as pipeline.py:527-2122 (in-scope paths), GPU-batched."""
-    import torch
-    from PIL import Image
-
-    from .frames import plan_groups, rank0_share, run_pipeline
-    t_setup = time.perf_counter()
-    from .postproc import LabSmoother, blend_frames
-
-    # one GPU per rank (several ranks may share a device with --dist_backend gloo: tests)
-    dev = torch.device("cuda", rank % torch.cuda.device_count() if world > 1 else torch.cuda.current_device())
-    torch.cuda.set_device(dev)
-    blend = float(max(0.0, min(1.0, blend)))
-    save_map = save_map or {}
-
-    # ---- models: A + optional B..H (RGB blend, pipeline.py:1872-1879) ----
+def load_stylizer(args, model_path, io_preset: str, dev):
+    """Model A + optional B..H (RGB blend, pipeline.py:1872-1879), the region compositor and the blend weights
+    -> (frame_loop.Stylizer, the io_preset in force)."""
     slots, slot_letters = [], []
     model_a, arch_a = load_model(str(model_path), args.model_type, dev, args.dtype, "A")
     if arch_a == "nst" and io_preset in ("auto", "raw_255", "imagenet_255"):  # pipeline.py:610-614
@@ -565,62 +403,45 @@ def style_frames(args, frames_dir: Optional[Path], model_path, output_prefix: st
         from .regions import RegionCompositor
         regions = RegionCompositor(args, dev)
         _log(f"[region] mode={args.region_mode} optimize={regions.optimized} seed={regions.seed}")
+    lab = None
     if n_blend > 1 and getattr(args, "blend_models_lab", False):
         # LAB blend (pipeline.py:1841-1870): L from A, a/b from the weighted mix of the others
         lab_wl, lab_wab = parse_lab_weights(getattr(args, "blend_models_lab_weights", None))
         lab_rest = lab_weights_rest(args.blend_models_weights, n_blend)
-        weights = [lab_wl, lab_wab] + lab_rest
+        weights, lab = [lab_wl, lab_wab] + lab_rest, (lab_wl, lab_wab, lab_rest)
         _log(f"[blend] LAB blend: L={lab_wl},ab={lab_wab},rest={lab_rest}")
     else:
         weights = parse_blend_weights(args.blend_models_weights, n_blend) if n_blend > 1 else [1.0]
-    _log(f"[cfg] io_preset={io_preset} models={len(slots)} weights={weights} dtype={args.dtype} gpus={world} batch={args.batch}")
+    return frame_loop.Stylizer(slots, slot_letters, n_blend, weights, lab, regions), io_preset
+
+
+# ----------------------------------------------------------------------------- the frame loop
+def style_frames(args, frames_dir: Optional[Path], model_path, output_prefix: str, image_ext_out: str, device_str: str,
+                 threads: int, stride: int, max_frames: Optional[int], smooth_lightness: bool, smooth_alpha: float,
+                 jpeg_quality: int, io_preset: str, smooth_chroma: bool = False, chroma_alpha: float = 0.85,
+                 blend: float = 1.0, image_mode: bool = False, save_map: Optional[Dict[int, str]] = None,
+                 rank: int = 0, world: int = 1):
+    """Same signature/behaviour as pipeline.py:527-2122 (in-scope paths), GPU-batched: builds the parts of
+    frame_loop.py and runs their stages."""
+    import torch
+
+    from .frames import agree_ok, plan_groups, rank0_share, run_pipeline, shard
+    t_setup = time.perf_counter()
+    from .postproc import LabSmoother
+
+    # one GPU per rank (several ranks may share a device with --dist_backend gloo: tests)
+    dev = torch.device("cuda", rank % torch.cuda.device_count() if world > 1 else torch.cuda.current_device())
+    torch.cuda.set_device(dev)
+    blend = float(max(0.0, min(1.0, blend)))
+    stylizer, io_preset = load_stylizer(args, model_path, io_preset, dev)
+    _log(f"[cfg] io_preset={io_preset} models={len(stylizer.slots)} weights={stylizer.weights} dtype={args.dtype} "
+         f"gpus={world} batch={args.batch}")
     _log(f">> smoothing: {smooth_lightness}  alpha={smooth_alpha}  |  blend={blend}")
-
-    # ---- frames ----
-    if args.synthetic:
-        m = re.match(r"^\s*(\d+)\s*[xX]\s*(\d+)\s*$", args.synthetic)
-        if not m:
-            _log(f"[error] --synthetic expects WxH, got {args.synthetic}")
-            sys.exit(2)
-        n_syn = int(args.synthetic_frames)
-        if max_frames:
-            n_syn = min(n_syn, int(max_frames))
-        src = FrameSource(synthetic=(n_syn, int(m.group(2)), int(m.group(1))))
-        names = [f"frame_{i + 1:04d}" for i in range(n_syn)]
-    else:
-        staged = getattr(args, "_staged_sources", None)
-        if staged is not None:  # --input_dir: frame_{i:04d} staged in memory (prepare); only .png/.jpg/.jpeg
-            # staged frames are styled (pipeline.py:1019-1021 filters frames_dir by suffix)
-            entries = [(f"frame_{i:04d}", s) for i, s in enumerate(staged, start=1)
-                       if Path(s[0]).suffix.lower() in {".png", ".jpg", ".jpeg"}]
-        else:
-            files = sorted(p for p in frames_dir.iterdir() if p.is_file() and p.name.startswith("frame_")
-                           and p.suffix.lower() in {".png", ".jpg", ".jpeg"})
-            entries = [(p.stem, p) for p in files]
-        if stride and stride > 1:
-            entries = entries[::stride]
-        if max_frames:
-            entries = entries[:max_frames]
-        if not entries:
-            _log(f"[error] No frames found to style in: {frames_dir}")
-            sys.exit(1)
-        ir = int(getattr(args, "inference_res", 0) or 0)
-        src = (FrameSource(staged=[e[1] for e in entries], infer_res=ir) if staged is not None
-               else FrameSource(files=[e[1] for e in entries], infer_res=ir))
-        names = [e[0] for e in entries]
-    _log(f"[debug] found {len(src)} staged frame(s)")
-
-    if getattr(args, "mask_dir", None) and not getattr(args, "mask", None) and not args.synthetic:
-        md = Path(args.mask_dir)
-        missing = [nm for nm in names if not (md / f"mask_{nm.split('_')[-1]}.png").exists()]
-        if missing and len(missing) == len(names):
-            _log(f"[mask][ERROR] --mask_dir set to {md} but no masks like mask_0001.png were found.")
-            sys.exit(2)
-        if missing:
-            _log(f"[mask][WARN] {len(missing)}/{len(names)} mask(s) missing under {md}.")
+    src, names = frame_loop.list_frames(args, frames_dir, stride, max_frames)
+    frame_loop.check_mask_dir(args, names)
 
     pool = ThreadPoolExecutor(max_workers=max(1, threads))
-    prof = _PipeProf()
+    prof = frame_loop.PipeProf()
     with prof("size_scan"):  # header reads (a PNG's EXIF lookup decodes it): on the pool
         sizes = list(pool.map(src.size, range(len(src))))
     # with --flow_ema rank 0 runs every frame's temporal stage (flow + fused EMA + LAB EMA + blend): a lighter share
@@ -631,508 +452,59 @@ def style_frames(args, frames_dir: Optional[Path], model_path, output_prefix: st
     r0 = rank0_share(world, bsz) if flow_mode else bsz
     caps = [r0] + [bsz] * (world - 1)
     groups = plan_groups(sizes, world, bsz, r0)
+    my_shards = [shard(g, world, rank, caps) for g in groups]  # one per group, empty where this rank has no frames
     need_orig = blend < 1.0 or bool(args.mask or args.mask_dir) or (flow_mode and bool(getattr(args, "motion_blend", False)))
-
-    # host decode runs ahead of the GPU: this rank's next group(s) are loading on the pool while a group is
-    # stylized (and the previous group's encodes drain), so decode, GPU step and encode overlap
-    from .frames import shard
-    my_shards = [shard(g, world, rank, caps) for g in groups]
-    shard_pos = {tuple(sh): k for k, sh in enumerate(my_shards) if sh}
-    loads = {}
-    prefetch_depth = 2
-
-    pinned = {}  # shard k -> page-locked [n, h, w, 3] the loaders decode into (one H2D copy per group, async)
-    # --jpeg_reader gpu: shard k -> (page-locked coefficient records [n, record_bytes], JpegInfo); the loaders only
-    # entropy-decode, the GPU rebuilds the frames (jpegio.py).  Not with --inference_res (host LANCZOS needs the
-    # pixels) or --input_dir staging (EXIF / re-encode round trip): those keep Pillow
-    jpeg_recs = {}
-    jpeg_gpu = (getattr(args, "jpeg_reader", "pil") == "gpu" and src.files is not None and src.staged is None
-                and src.infer_res == 0)
-
-    def _jpeg_shard(sh):
-        """the shard's file bytes and common JpegInfo when every frame is a fast-path JPEG of one geometry"""
-        from . import jpegio
-        if any(Path(src.files[f]).suffix.lower() not in (".jpg", ".jpeg") for f in sh):
-            return None
-        datas, info = [], None
-        for f in sh:
-            with open(src.files[f], "rb") as fh:
-                d = fh.read()
-            i = jpegio.probe(d)
-            if i is None or (info is not None and i != info) or (i.h, i.w) != tuple(sizes[f]):
-                return None
-            info = i
-            datas.append(d)
-        return datas, info
-
-    def _load_into(f, buf, j):
-        a, b = src.load(f)
-        np.copyto(buf[j], a)  # numpy releases the GIL for the copy
-        return None if b is a else b
-
-    def _submit(k):
-        if 0 <= k < len(my_shards) and my_shards[k] and k not in pinned:
-            sh = my_shards[k]
-            h0, w0 = sizes[sh[0]]
-            js = _jpeg_shard(sh) if jpeg_gpu else None
-            if js is not None:
-                from . import jpegio
-                rec = torch.empty((len(sh), js[1].record_bytes), dtype=torch.uint8, pin_memory=True)
-                pinned[k] = None
-                jpeg_recs[k] = (rec, js[1])
-                rn = rec.numpy()
-                for j, f in enumerate(sh):  # -> 0, or a code: the stream is not clean and the shard goes to Pillow
-                    loads[f] = pool.submit(jpegio.entropy_decode_into, js[0][j], rn[j])
-            elif all(sizes[f] == (h0, w0) for f in sh):
-                buf = torch.empty((len(sh), h0, w0, 3), dtype=torch.uint8, pin_memory=True)
-                pinned[k] = buf
-                bn = buf.numpy()
-                for j, f in enumerate(sh):
-                    loads[f] = pool.submit(_load_into, f, bn, j)
-            else:
-                pinned[k] = None
-                for f in sh:
-                    if f not in loads:
-                        loads[f] = pool.submit(src.load, f)
-
-    # the reference fits model A's output to the content size; with --inference_res the model
-    # input is smaller than the content
-    def stylize(idx: List[int]):
-        if not idx:
-            h0, w0 = sizes[0]
-            if flow_mode:
-                return torch.empty((0, 15 * h0 * w0), dtype=torch.uint8, device=dev)
-            return torch.empty((0, h0, w0, 6 if need_orig else 3), dtype=torch.uint8, device=dev)
-        k = shard_pos.get(tuple(idx), -1)
-        for j in range(k, k + 1 + prefetch_depth):
-            _submit(j)
-        buf = pinned.pop(k, None)
-        jrec = jpeg_recs.pop(k, None)
-        with prof("wait_decode"):
-            loaded = [(loads.pop(f) if f in loads else pool.submit(src.load, f)).result() for f in idx]
-            if jrec is not None and any(loaded):  # Pillow warns, raises or decodes the damaged file as it always did
-                jrec = None
-                loaded = [t.result() for t in [pool.submit(src.load, f) for f in idx]]
-        with prof("h2d"):
-            if jrec is not None:
-                from . import jpegio
-                orig = xin = jpegio.reconstruct_gpu(jrec[0].to(dev, non_blocking=True), jrec[1])
-            elif buf is not None:  # decoded straight into page-locked memory; loaded = the model inputs if different
-                orig = buf.to(dev, non_blocking=True)
-                xin = orig if loaded[0] is None else torch.from_numpy(np.stack(loaded)).to(dev)
-            else:
-                orig = torch.from_numpy(np.stack([a for a, _ in loaded])).to(dev, non_blocking=True)
-                xin = orig if loaded[0][1] is loaded[0][0] else torch.from_numpy(np.stack([b for _, b in loaded])).to(dev)
-        h0, w0 = orig.shape[1], orig.shape[2]
-        fids = [f + 1 for f in idx]  # the reference's 1-based frame index (animations, rotation)
-        if flow_mode:  # the temporal stage needs out01 before the ToPILImage truncation (pipeline.py:1884-1943)
-            out01 = _out01_f32(xin, orig, fids, h0, w0)
-            n = out01.shape[0]
-            return torch.cat([out01.view(torch.uint8).reshape(n, -1), orig.reshape(n, -1)], dim=1)
-        if regions is not None and regions.optimized:  # crops of the full-resolution frame (pipeline.py:1309)
-            styled = regions.optimized_frames(dict(zip(slot_letters, slots)), orig, fids)
-        elif regions is not None:
-            from .regions import Source, forward_raw
-            raw = [Source(forward_raw(m, xin, pr), pr) for m, pr in slots]
-            styled = regions.standard(raw, orig, fids, n_blend, (h0, w0))
-        elif n_blend == 1 and xin.shape[1:3] == orig.shape[1:3]:
-            styled = slots[0][0].stylize_frames(xin, slots[0][1])
-        elif n_blend == 1:
-            styled = _slot_u8(slots[0][0], slots[0][1], xin, h0, w0)
-        elif getattr(args, "blend_models_lab", False):
-            from .postproc import blend_models_lab
-            outs = [_slot_u8(m, pr, xin, h0, w0) for m, pr in slots[:n_blend]]
-            styled = blend_models_lab(outs, lab_rest, lab_wl, lab_wab)
-        else:
-            styled = _blend_slots(slots[:n_blend], weights, xin, h0, w0)
-        return torch.cat([styled, orig], dim=3) if need_orig else styled
-
-    def _out01_f32(xin, orig, fids, h0, w0):
-        """out01 [n,3,h0,w0] float32: the frame's styled result before ToPILImage (model A / RGB blend / LAB
-        blend / region composite), for the temporal stage."""
-        from .regions import Source, composite, crop_input, forward_raw
-        if regions is not None and regions.optimized:
-            return regions.optimized_frames(dict(zip(slot_letters, slots)), orig, fids, out_f32=True)
-        if regions is not None:
-            raw = [Source(forward_raw(m, xin, pr), pr) for m, pr in slots]
-            return regions.standard(raw, orig, fids, n_blend, (h0, w0), out_f32=True)
-        if n_blend > 1 and getattr(args, "blend_models_lab", False):  # to_tensor of the LAB-blended image
-            from .postproc import blend_models_lab
-            outs = [_slot_u8(m, pr, xin, h0, w0) for m, pr in slots[:n_blend]]
-            u8 = blend_models_lab(outs, lab_rest, lab_wl, lab_wab)
-            return crop_input(u8, (0, 0, w0, h0), (h0, w0))
-        # model A alone, or the RGB blend: zeros + w_i * out_i, clamp -- one all-ones region of the compositor
-        raw = [Source(forward_raw(m, xin, pr), pr) for m, pr in slots[:n_blend]]
-        ones = torch.ones((1, h0, w0), dtype=torch.float32, device=dev)
-        return composite(raw, [[(i, w) for i, w in enumerate(weights[:n_blend])]], ones, None, out_f32=True)
-
     lab = LabSmoother(dev, smooth_lightness, smooth_alpha, smooth_chroma, chroma_alpha)
     flow = None
     if flow_mode:
         from .temporal import FlowSmoother
         flow = FlowSmoother(True, float(args.flow_alpha), max(1, int(args.flow_downscale or 1)), args.flow_method)
-    mask_cache = {}
-    pending = []
-    t_start = time.perf_counter()
-    done = [0]
-
-    # Output stages (frames.run_pipeline).  The frame's owner stylizes it and, at the end, D2Hs and encodes it on its
-    # own PCIe link and host pool; the only ordered work is the LAB EMA (pipeline.py:1942-1978), which rank 0 runs
-    # over the planes it smooths (1 byte per pixel by default) -- or, with --flow_ema, the whole temporal chain over
-    # [out01 | orig], returning finished frames.  Mask composite and blend (pipeline.py:1984-2092) run on the owner.
-    ordered_lab = (lab.sl or lab.sc) and not flow_mode
-
-    def stylize_send(idx: List[int]):
-        full = stylize(idx)
-        if flow_mode:
-            return full, None
-        if ordered_lab:
-            return lab.planes(full[..., :3] if need_orig else full), full
-        return None, full
-
-    def root_post(g: List[int], full):
-        h0, w0 = sizes[g[0]]
-        if lab.hw is not None and lab.hw != (h0, w0):
-            _log(f"[size][reset] frame dims changed {lab.hw} -> {(h0, w0)}; resetting EMA caches")
-            lab.reset()
-            if flow is not None:
-                flow.reset()
-        if not flow_mode:
-            return lab.smooth_planes(full, (h0, w0)) if ordered_lab else None
-        # unpack [out01 f32 | orig u8] and run the temporal stage in frame order
-        from .temporal import motion_alpha, planar_to_u8
-        nb = 3 * h0 * w0 * 4
-        out01 = full[:, :nb].contiguous().view(torch.float32).reshape(len(g), 3, h0, w0)
-        orig = full[:, nb:].contiguous().reshape(len(g), h0, w0, 3)
-        # None for the first frame of a run (no previous frame); the batch's flows come in one call
-        fused, flows = flow.batch(out01, orig)
-        motion = None
-        if getattr(args, "motion_blend", False):  # pipeline.py:2072-2080 alpha from this frame's flow
-            motion = [None if fl is None else motion_alpha(fl, blend) for fl in flows]
-        styled = lab(planar_to_u8(torch.stack(fused)))
-        lab.hw = (h0, w0)
-        if need_orig:
-            styled_in = styled
-            styled = blend_frames(styled, orig, blend, _masks_for(g, h0, w0), args.composite_mode)
-            if motion is not None:  # frames with a flow and no mask: the motion-adaptive blend replaces it
-                for j, f in enumerate(g):
-                    if motion[j] is not None and not _has_mask(f):
-                        styled[j:j + 1] = blend_frames(styled_in[j:j + 1], orig[j:j + 1], 1.0, motion[j][None], "keep")
-        return styled
-
-    def ret_spec(g: List[int]):
-        h0, w0 = sizes[g[0]]
-        if flow_mode:
-            return (h0, w0, 3), torch.uint8
-        return ((lab.nplanes, h0 * w0), torch.uint8) if ordered_lab else None
-
-    def emit(idx: List[int], rows, full):
-        if not idx:
-            return
-        if flow_mode:
-            styled = rows
-        else:
-            styled = full[..., :3].contiguous() if need_orig else full
-            if ordered_lab:
-                styled = lab.merge(styled, rows)
-            if need_orig:
-                h0, w0 = styled.shape[1], styled.shape[2]
-                styled = blend_frames(styled, full[..., 3:].contiguous(), blend, _masks_for(idx, h0, w0),
-                                      args.composite_mode)
-        gpu_png = (getattr(args, "png_writer", "pil") == "gpu" and not args.no_save
-                   and getattr(args, "png_compress_level", None) is None and not any(_out_path(f)[1] for f in idx))
-        # --jpeg_writer gpu: per group, when every frame of it is saved as a JPEG at a quality libjpeg takes as given
-        gpu_jpeg = (getattr(args, "jpeg_writer", "pil") == "gpu" and not args.no_save
-                    and 1 <= int(jpeg_quality) <= 100 and all(_out_path(f)[1] for f in idx))
-        gpu_files = gpu_png or gpu_jpeg
-        with prof("d2h"):
-            # page-locked D2H on a copy stream behind the frames' last kernel; the encoders wait for its event, so
-            # this thread goes on queueing the next group's forward instead of waiting for the GPU.  --png_writer gpu
-            # and --jpeg_writer gpu: the group's finished files (and their sizes) instead of the pixels
-            if gpu_png:
-                from .pngio import encode_png_gpu
-                src, sizes_d = encode_png_gpu(styled)
-            elif gpu_jpeg:
-                from .jpegio import encode_jpeg_gpu
-                src, sizes_d = encode_jpeg_gpu(styled, int(jpeg_quality),
-                                               _jpeg_slot_bytes(styled.shape[1], styled.shape[2]))
-            else:
-                src, sizes_d = styled, None
-            host_t = torch.empty(src.shape, dtype=torch.uint8, pin_memory=True)
-            host_sz = torch.empty(src.shape[0], dtype=torch.int64, pin_memory=True) if gpu_files else None
-            copy_stream.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(copy_stream):
-                host_t.copy_(src, non_blocking=True)
-                if gpu_files:
-                    host_sz.copy_(sizes_d, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(copy_stream)
-            src.record_stream(copy_stream)
-            if gpu_files:
-                sizes_d.record_stream(copy_stream)
-        # one waiter thread per run waits for the copy's event and then hands the frames to the encoder pool, so no
-        # pool thread sits blocked on the GPU (the pool also decodes the next groups).  A JPEG group keeps its pixels
-        # on the device until then: a frame whose file outgrew the copied slot is saved from them
-        pending.append(waiter.submit(_hand_off, ev, host_t, list(idx) if not args.no_save else [], host_sz,
-                                     styled if gpu_jpeg else None))
-        del host_t  # the waiter holds it until the copy is done; the savers' row views keep it alive after that
-        _reap_pending()
-        if not args.no_save:
-            written.extend(idx)
-        done[0] += len(idx)
-        el = time.perf_counter() - t_start
-        who = f" rank {rank}" if world > 1 else ""
-        _log(f"[frame]{who} {done[0]}/{len(src) if world == 1 else sum(len(sh) for sh in my_shards)} styled  "
-             f"({done[0] / max(el, 1e-9):.2f} frames/s)")
-
-    def _has_mask(f):  # pipeline.py:1985-1993 mask_used: a --mask, or this frame's --mask_dir file exists
-        if getattr(args, "mask", None):
-            return True
-        if not getattr(args, "mask_dir", None) or args.synthetic:
-            return False
-        return (Path(args.mask_dir) / f"mask_{names[f].split('_')[-1]}.png").exists()
-
-    def _masks_for(g, h0, w0):
-        mfile_global = getattr(args, "mask", None)
-        if not mfile_global and not getattr(args, "mask_dir", None):
-            return None
-        ms = []
-        any_mask = False
-        for f in g:
-            mfile = mfile_global
-            if not mfile and not args.synthetic:
-                cand = Path(args.mask_dir) / f"mask_{names[f].split('_')[-1]}.png"
-                mfile = str(cand) if cand.exists() else None
-            if mfile is None:
-                # no mask for this frame -> no composite (pipeline.py:1985-1993): the alpha that
-                # leaves S unchanged is 1 for 'keep' and 0 for 'replace'
-                ident = 1.0 if args.composite_mode == "keep" else 0.0
-                ms.append(torch.full((h0, w0), ident, dtype=torch.float32, device=dev))
-                continue
-            any_mask = True
-            key = (mfile, h0, w0)
-            if key not in mask_cache:
-                # pipeline.py:2001-2003: feather radius from --mask_feather_pct of the target height,
-                # at least --mask_feather; the Gaussian feather runs on the GPU (nst_mask_feather)
-                fpx = _pct_to_px(getattr(args, "mask_feather_pct", 0.0) or 0.0, h0)
-                if getattr(args, "mask_feather", 0) and args.mask_feather > 0:
-                    fpx = max(fpx, int(args.mask_feather))
-                m8 = load_mask_u8(mfile, (h0, w0), bool(args.mask_invert), bool(args.mask_autofix),
-                                  bool(args.mask_force_transpose))
-                if fpx > 0:
-                    from .postproc import feather_masks
-                    mask_cache[key] = feather_masks(torch.from_numpy(m8)[None].to(dev), fpx)[0]
-                else:
-                    mask_cache[key] = torch.from_numpy(m8.astype(np.float32) / 255.0).to(dev)
-            ms.append(mask_cache[key])
-        if not any_mask:
-            return None
-        return torch.stack(ms)
-
-    copy_stream = torch.cuda.Stream(dev)
-    waiter = ThreadPoolExecutor(max_workers=1)
-
-    def _hand_off(ev, host_t, idx, host_sz=None, styled=None):
-        ev.synchronize()
-        host = host_t.numpy()
-        # each save holds a row view of the page-locked buffer (numpy keeps the tensor as the view's base), so the
-        # buffer is released when the group's last save ends -- not held for the whole run
-        if host_sz is not None:  # finished PNG / JPEG files from the GPU: write their bytes
-            sz = host_sz.tolist()
-            futs = []
-            for j, f in enumerate(idx):
-                if sz[j] >= 0:
-                    futs.append(pool.submit(_write_file, host[j, :sz[j]], f))
-                else:  # the JPEG did not fit its slot (-1): the frame's pixels, encoded on the host as without the flag
-                    with torch.cuda.stream(copy_stream):
-                        px = styled[j].cpu().numpy()
-                    futs.append(pool.submit(_save, px, f))
-            return futs
-        return [pool.submit(_save, host[j], f) for j, f in enumerate(idx)]
-
-    saves = []  # save futures of handed-off groups, reaped as they finish (errors surface at the next reap)
-
-    def _reap_pending(final: bool = False):
-        keep = []
-        for p in pending:
-            if final or p.done():
-                saves.extend(p.result())
-            else:
-                keep.append(p)
-        pending[:] = keep
-        left = []
-        for q in saves:
-            if final or q.done():
-                q.result()
-            else:
-                left.append(q)
-        saves[:] = left
-
-    def _out_path(f: int):
-        """frame f's output file and whether it is a JPEG (pipeline.py:2099-2119)"""
-        save_as_jpg = image_ext_out.lower() == "jpg"
-        if image_mode and (f + 1) in save_map:
-            out_path = Path(save_map[f + 1])
-            save_as_jpg = out_path.suffix.lower() in (".jpg", ".jpeg")
-        else:
-            idx_str = names[f].split("_")[-1]
-            base = frames_dir if frames_dir is not None else Path(args.work_dir)
-            out_path = (base / f"{output_prefix}_{idx_str}").with_suffix(".jpg" if save_as_jpg else ".png")
-        return out_path, save_as_jpg
-
-    def _write_file(data: np.ndarray, f: int):
-        out_path, _ = _out_path(f)
-        out_path.parent.mkdir(parents=True, exist_ok=True)
-        with open(out_path, "wb") as fh:
-            fh.write(memoryview(data))
-        return str(out_path)
-
-    def _save(img: np.ndarray, f: int):
-        out_img = Image.fromarray(img)
-        out_path, save_as_jpg = _out_path(f)
-        out_path.parent.mkdir(parents=True, exist_ok=True)
-        if save_as_jpg:
-            out_img.save(out_path, format="JPEG", quality=int(jpeg_quality))
-        elif getattr(args, "png_compress_level", None) is not None:
-            out_img.save(out_path, compress_level=int(args.png_compress_level))
-        elif getattr(args, "png_writer", "pil") == "fast":  # same pixels as Pillow's file (pngio docstring)
-            from .pngio import write_png
-            write_png(out_path, img)
-        else:
-            out_img.save(out_path)
-        return str(out_path)
-
-    written: List[int] = []
-    if ordered_lab or flow_mode:
-        run_pipeline(groups, world, rank, stylize_send, root_post, emit, ret_spec, dev, caps)
+    paths = frame_loop.OutputPaths(names, frames_dir, args.work_dir, output_prefix, image_ext_out, image_mode,
+                                   save_map or {})
+    sink = frame_loop.Sink(args, paths, jpeg_quality, pool, prof, dev)
+    loop = frame_loop.FrameLoop(args, sizes, frame_loop.DecodeAhead(args, src, sizes, my_shards, pool, prof, dev),
+                                stylizer, frame_loop.Masks(args, names, dev), sink, lab, flow, blend, need_orig,
+                                total=len(src) if world == 1 else sum(len(s) for s in my_shards),
+                                who=f" rank {rank}" if world > 1 else "", dev=dev)
+    if loop.ordered:
+        run_pipeline(groups, world, rank, loop.stylize_send, loop.root_post, loop.emit, loop.ret_spec, dev, caps)
     else:  # no ordered stage: every rank runs its frames start to finish, no exchange
-        from .frames import agree_ok
-        for sh in my_shards:  # one entry per group on every rank (empty where this rank has no frames of it)
+        for mine in my_shards:
             err = None
-            if sh:
+            if mine:
                 try:
-                    _, full = stylize_send(sh)
-                    emit(sh, None, full)
+                    _, full = loop.stylize_send(mine)
+                    loop.emit(mine, None, full)
                 except Exception as e:  # noqa: BLE001 -- re-raised below, after the other ranks have heard of it
                     err = e
             if world > 1:  # keep the ranks in step on errors, as run_pipeline does (RankFailed on the healthy ones)
                 agree_ok(err is None, dev)
             if err is not None:
                 raise err
-    with prof("drain_saves"):
-        _reap_pending(final=True)
-    waiter.shutdown()
+    sink.drain()
     pool.shutdown()
     prof.report(rank)
-    el = time.perf_counter() - t_start
-    LAST_RUN_STATS.update(frames=len(src), seconds=el, setup_seconds=t_start - t_setup, rank=rank,
-                          written=[names[f] for f in written])
+    el = time.perf_counter() - loop.t_start
+    written = [names[f] for f in sink.written]
+    LAST_RUN_STATS.update(frames=len(src), seconds=el, setup_seconds=loop.t_start - t_setup, rank=rank, written=written)
     if os.environ.get("NST_PIPE_WRITTEN"):  # diagnostics: the frames this rank encoded and wrote (tests)
         import json
         with open(os.path.join(os.environ["NST_PIPE_WRITTEN"], f"rank{rank}.json"), "w") as fh:
-            json.dump({"rank": rank, "world": world, "written": [names[f] for f in written], "loop_seconds": el,
-                       "setup_seconds": t_start - t_setup}, fh)
+            json.dump({"rank": rank, "world": world, "written": written, "loop_seconds": el,
+                       "setup_seconds": loop.t_start - t_setup}, fh)
     if rank == 0:
         _log(f"Styled {len(src)}/{len(src)} frames in {el:.2f}s ({len(src) / max(el, 1e-9):.2f} frames/s)")
-
-
-def _jpeg_slot_bytes(h: int, w: int) -> int:
-    """--jpeg_writer gpu: bytes copied to the host per frame -- the encoder's worst case, but never more than the
-    frame's pixels (rounded up to the 16 bytes the encoder wants), so the copy is no larger than without the flag.
-    A file that outgrows the slot (nst_jpeg_encode_u8 reports -1) is encoded on the host instead."""
-    from .jpegio import jpeg_enc_bound
-    return min(jpeg_enc_bound(h, w), (h * w * 3 + 15) // 16 * 16)
-
-
-class _PipeProf:
-    """Wall time of the frame loop's host-side phases on the main thread (NST_PIPE_PROF=1 prints them)."""
-
-    def __init__(self):
-        self.on = os.environ.get("NST_PIPE_PROF", "0") == "1"
-        self.t: Dict[str, float] = {}
-
-    def __call__(self, name: str):
-        import contextlib
-
-        if not self.on:
-            return contextlib.nullcontext()
-
-        @contextlib.contextmanager
-        def cm():
-            t0 = time.perf_counter()
-            try:
-                yield
-            finally:
-                self.t[name] = self.t.get(name, 0.0) + time.perf_counter() - t0
-        return cm()
-
-    def report(self, rank: int):
-        if self.on:
-            _log(f"[pipe-prof rank {rank}] " + " ".join(f"{k}={v:.3f}s" for k, v in self.t.items()))
-
-
-def _slot_u8(model, preset, xin, h0, w0):
-    """One slot's frames as the reference's to_pil(out.clamp(0,1)): decoded, fitted to the content
-    size (bilinear, pipeline.py:1512-1516), clamped, truncated to uint8."""
-    import torch
-
-    from . import _lib
-    from ._lib import check, lib
-    dev = xin.device
-    eng = model.engine(dev)
-    n, h, w, _ = xin.shape
-    oh, ow = eng.output_hw(h, w)
-    if (oh, ow) == (h, w) == (h0, w0):
-        return model.stylize_frames(xin, preset)
-    y = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=dev)
-    eng.forward_into(xin, _lib.NST_IO_U8_NHWC, n, h, w, _lib.PRESETS[preset], y, _lib.NST_IO_F32_NCHW)
-    out = torch.empty((n, h0, w0, 3), dtype=torch.uint8, device=dev)
-    check(lib().nst_decode_resize_u8(y.data_ptr(), n, oh, ow, _lib.PRESETS[preset], out.data_ptr(), h0, w0,
-                                     _lib.stream_ptr(dev)), "nst_decode_resize_u8")
-    return out
-
-
-def _blend_slots(slots, weights, xin, h0, w0):
-    """Raw f32 outputs of every slot -> nst_blend_models_u8 (decode, fit, weighted sum, clamp, truncation)."""
-    import ctypes
-
-    import torch
-
-    from . import _lib
-    from ._lib import check, lib
-    dev = xin.device
-    ys, presets = [], []
-    for model, preset in slots:
-        eng = model.engine(dev)
-        n, h, w, _ = xin.shape
-        oh, ow = eng.output_hw(h, w)
-        y = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=dev)
-        eng.forward_into(xin, _lib.NST_IO_U8_NHWC, n, h, w, _lib.PRESETS[preset], y, _lib.NST_IO_F32_NCHW)
-        ys.append(y)
-        presets.append(_lib.PRESETS[preset])
-    shapes = {tuple(y.shape) for y in ys}
-    if len(shapes) != 1:
-        raise _lib.NstError(f"model outputs differ in size {shapes}: the reference cannot blend them either")
-    m = len(ys)
-    out = torch.empty((xin.shape[0], h0, w0, 3), dtype=torch.uint8, device=dev)
-    yp = (ctypes.c_void_p * m)(*[y.data_ptr() for y in ys])
-    pr = (ctypes.c_int * m)(*presets)
-    wt = (ctypes.c_float * m)(*[float(np.float32(w)) for w in weights])
-    n, _, oh, ow = ys[0].shape
-    check(lib().nst_blend_models_u8(yp, pr, wt, m, n, oh, ow, out.data_ptr(), h0, w0, _lib.stream_ptr(dev)),
-          "nst_blend_models_u8")
-    return out
 
 
 # ----------------------------------------------------------------------------- main
 def _parse_canvas(s):
     if not s:
         return None
-    m = re.match(r"^\s*(\d+)\s*[xX]\s*(\d+)\s*$", str(s))
-    if not m:
+    wh = parse_wh(s)
+    if not wh:
         _log(f"[canvas][ERROR] Expected WxH (e.g., 1920x1080), got: {s}")
         sys.exit(2)
-    return int(m.group(1)), int(m.group(2))
+    return wh
 
 
 def prepare(args):

@@ -32,8 +32,9 @@ import torch
 
 from . import _lib
 from ._lib import NstError, check, lib
+from .pipeline import parse_blend_weights
 
-MODES = ("grid", "diagonal", "voronoi", "fractal", "radial", "waves", "spiral", "concentric", "random")
+MODES =("grid", "diagonal", "voronoi", "fractal", "radial", "waves", "spiral", "concentric", "random")
 MORPH_MODES = ("blob", "tentacle", "wave", "pulse")
 _MODEL_LETTERS = {"A": 0, "B": 1, "C": 2, "D": 3, "E": 4, "F": 5, "G": 6, "H": 7, "O": -1, "ORIGINAL": -1}
 _OFF = ("none", "static", "off", "0")
@@ -711,7 +712,6 @@ class RegionCompositor:
         weights = None
         if assignment == "weighted":
             try:
-                from .pipeline import parse_blend_weights
                 weights = parse_blend_weights(getattr(a, "blend_models_weights", None), num_models_quirk)
             except Exception:
                 weights = None

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import NstError, check, lib
+from .pipeline import assemble_video
 
 # fit(w, h) of a decoded w x h source -> ((x, y, cw, ch) to crop first or None, (tw, th) to resize to); it raises
 # NstError (the loader puts the file's path in front) for a source it cannot fit
@@ -100,7 +101,6 @@ def open_writer(args) -> FrameWriter:
 def close_run(tag: str, wr: FrameWriter, fps, video: Optional[str]) -> None:
     """The end of a CLI run: the frames assembled into `video` with ffmpeg if one was asked for, and the count line."""
     if video:
-        from .pipeline import assemble_video
         assemble_video(wr.dir, Path(video), fps, None, wr.prefix)
     print(f"[{tag}] wrote {wr.count} frames to {wr.dir}")
 

@@ -3,8 +3,6 @@ must equal Pillow's Image.open(f).convert("RGB") (the reference's reader, pipeli
 byte, and the CLI with --jpeg_reader gpu must write the files --jpeg_reader pil writes."""
 import ctypes
 import io
-import shutil
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -12,6 +10,7 @@ import torch
 from PIL import Image
 
 from neuralstyletransferv1_amd import _lib, jpegio, synthetic
+from cli_run import run_frames_dir
 from jpeg_ref import content, encode, pillow_rgb
 
 pytestmark = pytest.mark.gpu
@@ -101,22 +100,8 @@ def test_gpu_jpeg_rejects_small_workspace_and_wrong_record_size():
 
 
 def _cli(tmp_path, tag, frames_dir, reader, extra, batch=2):
-    """the video path's frame loop (pipeline._run_style over work_dir/frames, as pipeline.main runs it after the
-    extraction) -> the bytes of every styled file"""
-    from neuralstyletransferv1_amd import pipeline as P
-    wd = tmp_path / tag
-    fd = wd / "frames"
-    shutil.copytree(frames_dir, fd)
-    ck = tmp_path / "johnson.pth"
-    if not ck.exists():
-        torch.save(synthetic.make_state_dict("johnson", 2), ck)
-    a = P.build_parser().parse_args(["--input_video", "x", "--output_video", "y", "--work_dir", str(wd), "--model",
-                                     str(ck), "--io_preset", "imagenet_255", "--dtype", "bf16", "--batch", str(batch),
-                                     "--threads", "2", "--jpeg_reader", reader] + extra)
-    a.model_type = "transformer"
-    P._run_style(a, fd, Path(ck), {}, False)
-    outs = sorted(fd.glob("styled_frame_*.png"))
-    return [p.read_bytes() for p in outs]
+    """the frame loop with this reader -> the bytes of every styled file (all PNG here), in frame order"""
+    return list(run_frames_dir(tmp_path, tag, frames_dir, ["--jpeg_reader", reader] + extra, batch).values())
 
 
 def _frame_dir(tmp_path, variants):

@@ -2,14 +2,13 @@
 Image.fromarray(frame).save(f, format="JPEG", quality=q) writes (the reference's writer, pipeline.py:2099-2113) byte
 for byte, and the CLI with --jpeg_writer gpu must leave the files --jpeg_writer pil leaves."""
 import ctypes
-import shutil
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
-from neuralstyletransferv1_amd import _lib, jpegio, synthetic
+from neuralstyletransferv1_amd import _lib, jpegio
+from cli_run import run_frames_dir as _cli
 from jpeg_ref import content, encode
 
 pytestmark = pytest.mark.gpu
@@ -103,23 +102,6 @@ def test_encode_jpeg_gpu_rejects_other_layouts():
 
 
 # ---- the CLI ----
-def _cli(tmp_path, tag, frames_dir, extra):
-    """the video path's frame loop (pipeline._run_style over work_dir/frames) -> {file name: bytes} of the styled files"""
-    from neuralstyletransferv1_amd import pipeline as P
-    wd = tmp_path / tag
-    fd = wd / "frames"
-    shutil.copytree(frames_dir, fd)
-    ck = tmp_path / "johnson.pth"
-    if not ck.exists():
-        torch.save(synthetic.make_state_dict("johnson", 2), ck)
-    a = P.build_parser().parse_args(["--input_video", "x", "--output_video", "y", "--work_dir", str(wd), "--model",
-                                     str(ck), "--io_preset", "imagenet_255", "--dtype", "bf16", "--batch", "2",
-                                     "--threads", "2"] + extra)
-    a.model_type = "transformer"
-    P._run_style(a, fd, Path(ck), {}, False)
-    return {p.name: p.read_bytes() for p in sorted(fd.glob("styled_frame_*"))}
-
-
 @pytest.fixture()
 def frame_dir(tmp_path):
     d = tmp_path / "src_frames"
@@ -152,7 +134,7 @@ def test_cli_png_outputs_ignore_the_flag(tmp_path, frame_dir, monkeypatch):
 def test_cli_frame_that_outgrows_its_slot_is_saved_by_pillow(tmp_path, frame_dir, monkeypatch):
     """the slot patched to hold the smaller files of the run but not the larger: those frames come back as -1 and
     are saved from their pixels; every file still equals the Pillow writer's"""
-    from neuralstyletransferv1_amd import pipeline as P
+    from neuralstyletransferv1_amd import frame_loop
     common = ["--image_ext", "jpg", "--jpeg_quality", "100"]
     pil = _cli(tmp_path, "pil", frame_dir, common + ["--jpeg_writer", "pil"])
     lens = sorted(len(b) for b in pil.values())
@@ -163,7 +145,7 @@ def test_cli_frame_that_outgrows_its_slot_is_saved_by_pillow(tmp_path, frame_dir
     def small_slot(h, w):
         calls.append((h, w))
         return slot
-    monkeypatch.setattr(P, "_jpeg_slot_bytes", small_slot)
+    monkeypatch.setattr(frame_loop, "_jpeg_slot_bytes", small_slot)
     seen = []
     real = jpegio.encode_jpeg_gpu
 
